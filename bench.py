@@ -10,7 +10,18 @@ device; rank r of N holds global blocks [r n, (r + 1) n).  One
 of every block, util/crc32c.cc:286-329): one launch for the 1M-block config,
 back-to-back launches of 1M blocks for a 10M-block shard.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it fills the
+batch, spins the clock up, runs the W warm-up and the K timed steps, writes the
+outputs when --dump-outputs is given, and prints the result line.  --full adds
+the measurements that take runs of their own (listed under "Extra fields").
+--dump-outputs DIR writes what the last timed step returned, the CRC of every
+block in block order, as DIR/crc32c.npy (float64: every uint32 exactly); above
+2M blocks a fixed, seeded sample of 2M of them, their block indices beside them
+in DIR/crc32c_index.npy.  With N > 1 each rank writes crc32c.rank<r>.npy.  The
+inputs are a pure function of the arguments, so two builds compare output for
+output.
 
 With N > 1 it runs one process per GPU under torch.distributed.run: when
 WORLD_SIZE is unset, bench.py starts `python -m torch.distributed.run
@@ -24,14 +35,17 @@ steps between HIP events on the launch stream, barrier + synchronize, max over
 ranks.  Rank 0 prints ONE JSON line.
 
 Extra fields: roofline (achieved algorithmic GB/s of the dominant kernel vs the
-8 TB/s HBM peak), cpu_baseline (the reference CPU CRC on the host cores, rank 0
+8 TB/s HBM peak, from the HIP events around the timed steps), ranks
+(per rank: its own elapsed time, bytes, GiB/s and kernel time per launch, its
+device's PCI address and NUMA node and its CPUs' NUMA nodes; the bytes add up
+to the aggregate).  With --full only (null otherwise): the roofline's
+median_launch_ms / frac_at_median (every launch between its own pair of
+events, after the timed region), cpu_baseline (the reference CPU CRC on the host cores, rank 0
 at N=1 only, bounded sample), stream_read (the same buffer read with the CRC
 kernel's own access pattern and no CRC work: the measured read ceiling),
 host_staged (the same blocks checksummed from pinned host memory through
-lsbm_crc32c_batch_host: the PCIe-inclusive rate, rank 0 at N=1 only), ranks
-(per rank: its own elapsed time, bytes, GiB/s and kernel time per launch, its
-device's PCI address and NUMA node and its CPUs' NUMA nodes; the bytes add up
-to the aggregate).
+lsbm_crc32c_batch_host: the PCIe-inclusive rate, rank 0 at N=1 only).
+--no-cpu-baseline leaves cpu_baseline and host_staged out of a --full run.
 """
 import argparse
 import ctypes
@@ -59,13 +73,22 @@ def parse():
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--blocks", type=int, default=0, help=argparse.SUPPRESS)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure the median launch, the stream-read ceiling, the "
+                        "host-staged rate and the CPU baselines (runs of their own)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write the last timed step's CRCs to DIR/crc32c.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip cpu_baseline and host_staged")
     p.add_argument("--cpu-seconds", type=float, default=12.0,
                    help="aggregate CPU-seconds for the cpu_baseline sample")
     p.add_argument("--dump-samples", default="", help=argparse.SUPPRESS)  # tests: per-rank CRCs
     p.add_argument("--spin-s", type=float, default=0.5,
                    help="seconds of untimed launches before the warm-up steps (GPU clock ramp)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def usable_cores():
@@ -331,6 +354,23 @@ def host_staged(engine, data, gpu_crcs, n_blocks, reps=3):
             "mismatches_vs_device_path": int(np.count_nonzero(got != gpu_crcs[:n_blocks]))}
 
 
+DUMP_MAX = 1 << 21  # CRCs per rank in --dump-outputs (float64: 16 MiB, + 16 MiB of indices)
+
+
+def dump_outputs(path, out, n, rank, world):
+    """--dump-outputs: what the timed path returned in its last step (the
+    caller's `out`, one CRC per block), as float64 .npy.  A batch above
+    DUMP_MAX blocks is sampled at fixed, seeded block indices."""
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f".rank{rank}"
+    crc = out.cpu().numpy().view(np.uint32)
+    if n > DUMP_MAX:
+        idx = np.sort(np.random.default_rng(SEED + rank).choice(n, DUMP_MAX, replace=False))
+        crc = crc[idx]
+        np.save(os.path.join(path, f"crc32c_index{tag}.npy"), (rank * n + idx).astype(np.float64))
+    np.save(os.path.join(path, f"crc32c{tag}.npy"), crc.astype(np.float64))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -400,29 +440,34 @@ def main():
                         mark_start=lambda: ev0.record(stream), mark_end=lambda: ev1.record(stream))
     kern_ms = ev0.elapsed_time(ev1)  # the K launches, HIP events on the launch stream
 
-    # per-launch HIP events after the timed region (SURVEY.md 8d asks for the
-    # median launch): each launch bracketed by its own pair of events
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-           for _ in range(max(3, args.steps))]
-    for a, b in evs:
-        a.record(stream)
-        step()
-        b.record(stream)
-    torch.cuda.synchronize()
-    per_launch_ms = sorted(a.elapsed_time(b) for a, b in evs)
-    median_ms = per_launch_ms[len(per_launch_ms) // 2]
+    if args.dump_outputs:  # (before anything below writes `out` again)
+        dump_outputs(args.dump_outputs, out, n, rank, world)
 
-    # stream-read ceiling on the same buffer (same stream, same events)
-    sink = torch.zeros(1024, dtype=torch.int32, device="cuda")
-    for _ in range(3):
-        engine.stream_read(data, sink, stream=stream)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    for _ in range(10):
-        engine.stream_read(data, sink, stream=stream)
-    e1.record(stream)
-    torch.cuda.synchronize()
-    stream_gbps = 10 * n * BLOCK / (e0.elapsed_time(e1) / 1e3) / 1e9
+    median_ms = stream_gbps = None
+    if args.full:
+        # per-launch HIP events after the timed region (SURVEY.md 8d asks for the
+        # median launch): each launch bracketed by its own pair of events
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+               for _ in range(max(3, args.steps))]
+        for a, b in evs:
+            a.record(stream)
+            step()
+            b.record(stream)
+        torch.cuda.synchronize()
+        per_launch_ms = sorted(a.elapsed_time(b) for a, b in evs)
+        median_ms = per_launch_ms[len(per_launch_ms) // 2]
+
+        # stream-read ceiling on the same buffer (same stream, same events)
+        sink = torch.zeros(1024, dtype=torch.int32, device="cuda")
+        for _ in range(3):
+            engine.stream_read(data, sink, stream=stream)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(10):
+            engine.stream_read(data, sink, stream=stream)
+        e1.record(stream)
+        torch.cuda.synchronize()
+        stream_gbps = 10 * n * BLOCK / (e0.elapsed_time(e1) / 1e3) / 1e9
 
     # per rank: its own elapsed time, bytes and rate, and where its GPU and
     # CPUs sit (the aggregate `value` alone hides a slow rank)
@@ -450,7 +495,7 @@ def main():
                  xor_block=xb, xor_crc=xc)
 
     cpu = staged = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         gpu_crcs = out.cpu().numpy().view(np.uint32)
         staged = host_staged(engine, data, gpu_crcs, min(n, 1 << 18))
         cpu = cpu_baseline(data.cpu().numpy(), gpu_crcs, args.cpu_seconds)
@@ -463,6 +508,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(t_max * 1e3 / args.steps, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -485,10 +531,10 @@ def main():
                          "kernel": "crc32c_fixed_kernel<false,32>",
                          "algorithmic_bytes_per_launch": n * BLOCK,
                          "avg_launch_ms": round(per_launch_s * 1e3, 4),
-                         "median_launch_ms": round(median_ms, 4),
-                         "frac_at_median": round(n * BLOCK / (median_ms / 1e3) / 1e9 / HBM_PEAK_GBPS, 4)},
-            "stream_read": {"GBps": round(stream_gbps, 1),
-                            "crc_frac_of_stream_read": round(achieved / stream_gbps, 4)},
+                         "median_launch_ms": median_ms and round(median_ms, 4),
+                         "frac_at_median": median_ms and round(n * BLOCK / (median_ms / 1e3) / 1e9 / HBM_PEAK_GBPS, 4)},
+            "stream_read": stream_gbps and {"GBps": round(stream_gbps, 1),
+                                            "crc_frac_of_stream_read": round(achieved / stream_gbps, 4)},
             "cpu_baseline": cpu,
             "host_staged": staged,
             "ranks": ranks,

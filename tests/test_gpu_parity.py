@@ -646,7 +646,8 @@ def test_level2_binding_over_the_reference_table_code(torch_cuda):
                        "gpu_binding")
     if not os.access(exe, os.X_OK):
         pytest.skip("oracle/_ref/gpu_binding not built (needs /root/reference at build time)")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    from test_ref_link import ref_env
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=ref_env())
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.startswith("OK"), r.stdout
 
@@ -677,7 +678,8 @@ def test_gpu_sealed_table_builder_matches_the_reference_table_builder(torch_cuda
                        "gpu_table_builder")
     if not os.access(exe, os.X_OK):
         pytest.skip("oracle/_ref/gpu_table_builder not built (needs /root/reference at build time)")
-    r = subprocess.run([exe, "3"], capture_output=True, text=True, timeout=300)
+    from test_ref_link import ref_env
+    r = subprocess.run([exe, "3"], capture_output=True, text=True, timeout=300, env=ref_env())
     print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAIL" not in r.stdout and r.stdout.strip().splitlines()[-1].startswith("OK"), r.stdout
@@ -701,7 +703,8 @@ def test_compaction_end_to_end_with_both_gpu_ends_matches_the_reference(torch_cu
                        "gpu_compaction")
     if not os.access(exe, os.X_OK):
         pytest.skip("oracle/_ref/gpu_compaction not built (needs /root/reference at build time)")
-    r = subprocess.run([exe, "4", "16", "16"], capture_output=True, text=True, timeout=300)
+    from test_ref_link import ref_env
+    r = subprocess.run([exe, "4", "16", "16"], capture_output=True, text=True, timeout=300, env=ref_env())
     print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
     last = r.stdout.strip().splitlines()[-1]
@@ -727,7 +730,7 @@ def test_db_bench_gpu_tables(torch_cuda, tmp_path):
     import hashlib
     import os
     import subprocess
-    from test_ref_link import db_bench_args, db_verify
+    from test_ref_link import db_bench_args, db_verify, ref_env
     ref = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref")
     if not all(os.access(os.path.join(ref, x), os.X_OK) for x in ("db_bench", "db_bench_gpu", "db_verify")):
         pytest.skip("oracle/_ref/db_bench* not built (needs /root/reference at build time)")
@@ -735,7 +738,7 @@ def test_db_bench_gpu_tables(torch_cuda, tmp_path):
     for name in ("db_bench", "db_bench_gpu"):
         db = tmp_path / name
         db.mkdir()
-        env = dict(os.environ, LSBM_TABLE_STATS="1")
+        env = ref_env(LSBM_TABLE_STATS="1")
         r = subprocess.run([os.path.join(ref, name)] + db_bench_args(str(db), 1_000_000),
                            capture_output=True, text=True, timeout=300, env=env)
         assert r.returncode == 0, r.stderr[-3000:]

@@ -17,6 +17,19 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
+# every oracle/_ref binary that takes symbols from lsbm_amd/liblsbm_crc32c.so
+LSBM_LINKED = ("link_lsbm", "gpu_binding", "gpu_table_builder", "gpu_compaction", "gpu_compaction_l1",
+               "db_bench_l1", "db_bench_gpu")
+
+
+def ref_env(**extra):
+    """Environment for running an oracle/_ref binary: this tree's lsbm_amd/
+    first on the loader's path, so the binary loads the library under test
+    wherever oracle/_ref was built or however it is mounted (its own run path,
+    $ORIGIN/../../lsbm_amd, covers a plain copy of the tree)."""
+    lib = os.path.join(REPO, "lsbm_amd")
+    old = os.environ.get("LD_LIBRARY_PATH")
+    return dict(os.environ, LD_LIBRARY_PATH=lib + (":" + old if old else ""), **extra)
 
 
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "table")), reason="needs /root/reference")
@@ -27,7 +40,7 @@ def test_reference_table_and_log_link_unchanged(tmp_path):
         d = tmp_path / v
         d.mkdir()
         r = subprocess.run([os.path.join(REPO, "oracle", "_ref", "link_" + v), str(d)],
-                           capture_output=True, text=True, timeout=120)
+                           capture_output=True, text=True, timeout=120, env=ref_env())
         assert r.returncode == 0, r.stderr
         # drop the reference's cache-statistics line (it carries a timestamp)
         outs[v] = [ln for ln in r.stdout.splitlines() if not ln.startswith("total:")]
@@ -80,6 +93,26 @@ def test_gpu_table_builder_compiles_and_links_against_the_reference():
     assert any("SealBlocks" in u for u in undefined)  # from liblsbm_crc32c.so
     ldd = subprocess.run(["ldd", exe], capture_output=True, text=True).stdout
     assert "liblsbm_crc32c.so" in ldd and "libamdhip64" in ldd
+
+
+@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "table")), reason="needs /root/reference")
+def test_ref_binaries_find_the_library_in_a_copy_of_the_tree(tmp_path):
+    """The oracle/_ref binaries are built in one place and run in another: in a
+    copy of oracle/_ref and lsbm_amd/ under another directory, with nothing in
+    the environment pointing anywhere, each resolves liblsbm_crc32c.so to the
+    copy beside it (run path $ORIGIN/../../lsbm_amd), not to the build tree."""
+    import shutil
+    subprocess.run(["make", "-s", "-j8", "-C", os.path.join(REPO, "oracle"),
+                    "reflink", "gpubind", "gputable", "gpucompact", "dbbench_gpu"], check=True)
+    (tmp_path / "oracle" / "_ref").mkdir(parents=True)
+    (tmp_path / "lsbm_amd").mkdir()
+    lib = shutil.copy(os.path.join(REPO, "lsbm_amd", "liblsbm_crc32c.so"), tmp_path / "lsbm_amd")
+    env = {k: v for k, v in os.environ.items() if k != "LD_LIBRARY_PATH"}
+    for name in LSBM_LINKED:
+        exe = shutil.copy(os.path.join(REPO, "oracle", "_ref", name), tmp_path / "oracle" / "_ref")
+        ldd = subprocess.run(["ldd", str(exe)], capture_output=True, text=True, env=env).stdout
+        found = [ln.split("=>")[1].split()[0] for ln in ldd.splitlines() if "liblsbm_crc32c.so" in ln and "=>" in ln]
+        assert found and os.path.realpath(found[0]) == os.path.realpath(lib), (name, ldd)
 
 
 # config 1 (BASELINE.json configs[0]): lsbm's own db_bench write workload
@@ -147,7 +180,7 @@ def test_db_bench_builds_three_ways_and_level1_writes_the_same_database(tmp_path
         db = tmp_path / name
         db.mkdir()
         r = subprocess.run([os.path.join(ref, name)] + db_bench_args(str(db), 200_000),
-                           capture_output=True, text=True, timeout=600)
+                           capture_output=True, text=True, timeout=600, env=ref_env())
         assert r.returncode == 0, r.stderr[-2000:]
         assert "separate" in r.stdout
         rc, v = db_verify(os.path.join(ref, "db_verify"), str(db))
