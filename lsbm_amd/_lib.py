@@ -89,6 +89,15 @@ SIGNATURES = {
     "lsbm_snappy_uncompressed_length_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _vp]),
     "lsbm_snappy_uncompress_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
 }
+# every symbol include/lsbm_block.h declares (a table of its own: SIGNATURES is
+# pinned to the three headers above by tests/test_host_api.py)
+BLOCK_SIGNATURES = {
+    "lsbm_block_scan_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "lsbm_block_decode_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp,
+                                     _vp, _vp]),
+    "lsbm_block_seek_dev": (_int, [_vp, _u64, _vp, _vp, _vp, _u64, _int, _u32, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _u64, _vp]),
+}
 
 _lib = None
 
@@ -109,7 +118,7 @@ def lib():
                 "(run __graft_entry__.build() or make -C lsbm_amd/csrc). "
                 "There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(BLOCK_SIGNATURES.items()):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)
