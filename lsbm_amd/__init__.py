@@ -7,12 +7,14 @@
   lsbm_amd.bloom    SSTable bloom filters: batched CreateFilter / KeyMayMatch / filter blocks
   lsbm_amd.snappy   SSTable block compression: batched snappy RawCompress / RawUncompress
   lsbm_amd.block    SSTable block reader: batched Block::Iter scan / decode / Seek, Table::InternalGet
+  lsbm_amd.block_build  SSTable block builder: batched flush plan, BlockBuilder Add / Finish, index
+                    blocks, whole table files
 
 The compute lives in lsbm_amd/liblsbm_crc32c.so (hand-written gfx950 HIP
 kernels behind the C ABIs in include/lsbm_crc32c.h, include/lsbm_bloom.h, include/lsbm_snappy.h and
-include/lsbm_block.h).
+include/lsbm_block.h, include/lsbm_block_build.h).
 """
 from ._lib import LIB_PATH, LsbmError, lib  # noqa: F401
 
 __all__ = ["LIB_PATH", "LsbmError", "lib", "crc32c", "engine", "table", "log", "bloom", "snappy",
-           "block"]
+           "block", "block_build"]

@@ -98,6 +98,16 @@ BLOCK_SIGNATURES = {
     "lsbm_block_seek_dev": (_int, [_vp, _u64, _vp, _vp, _vp, _u64, _int, _u32, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _u64, _vp]),
 }
+# every symbol include/lsbm_block_build.h declares
+BLOCK_BUILD_SIGNATURES = {
+    "lsbm_block_plan_scratch_bytes": (_u64, [_u64, _u64]),
+    "lsbm_block_plan_dev": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _u64, _u64, _u32, _vp, _vp, _u64, _vp,
+                                   _vp, _vp, _u64, _vp]),
+    "lsbm_block_build_dev": (_int, [_vp, _u64, _vp, _vp, _vp, _u64, _u64, _vp, _u64, _u32, _vp, _u64, _vp,
+                                    _vp, _vp, _vp]),
+    "lsbm_index_block_build_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _int, _vp, _u64,
+                                          _vp, _vp, _vp, _vp]),
+}
 
 _lib = None
 
@@ -118,7 +128,8 @@ def lib():
                 "(run __graft_entry__.build() or make -C lsbm_amd/csrc). "
                 "There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(BLOCK_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(BLOCK_SIGNATURES.items())
+                                  + list(BLOCK_BUILD_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)
