@@ -45,6 +45,7 @@ extern "C" {
 #define LSBM_ERR_HIP (-3)         /* a HIP runtime call failed */
 #define LSBM_ERR_NOMEM (-4)       /* device or pinned allocation failed */
 #define LSBM_ERR_CORRUPTION (-5)  /* verify found >= 1 mismatching block */
+#define LSBM_ERR_QUEUE_FAULT (-6) /* a kernel's work queue gave up a wait earlier: results were lost (sticky) */
 
 /* ---- flags ---- */
 #define LSBM_CRC32C_MASKED 0x1u /* out = Mask(crc) (util/crc32c.h:31-34) */
@@ -207,10 +208,27 @@ int lsbm_test_fail_host_pipeline(int chunks);
  * batch it takes.  Results are identical; for tests and A/B runs. */
 int lsbm_test_ragged_kernel(int which);
 
-/* Testing / A/B: the fixed-stride kernel's cross-XCC work queue on (1) or off
- * (0, the static interleave); -1 restores the default (LSBM_FIXED_QUEUE,
- * off). */
+/* Testing / A/B: the fixed-stride kernel's schedule across XCDs: 0 the static
+ * interleave, 1 the full cross-XCC work queue (every row past the first), 2
+ * the tail queue (the static interleave, the last rows from the queue); -1
+ * restores the default (LSBM_FIXED_QUEUE, same values; unset: 2). */
 int lsbm_test_fixed_queue(int on);
+/* Testing: the tail queue's minimum rows (groups per wave) of a launch and the
+ * rows it hands out through the queue, so that small batches reach the tail
+ * path; (-1, -1) restores the defaults. */
+int lsbm_test_fixed_tail(int min_rows, int tail_rows);
+/* Testing: sets (1) or clears (0) `device`'s sticky queue-fault word, which a
+ * wave of the cross-XCC queue sets when it runs into its spin cap; while set,
+ * every call on the device returns LSBM_ERR_QUEUE_FAULT.  Returns the word's
+ * previous value, -1 for a bad argument.  Needs no device. */
+int lsbm_test_queue_fault(int device, int value);
+/* Testing / A/B: the queue's heads come from the device's pool of head sets,
+ * which the kernels hand back zeroed (1, the default), or from per-call scratch
+ * zeroed in stream order (0). */
+int lsbm_test_queue_pool(int on);
+/* Testing: the number of `device`'s pooled head sets that are in use (0 once
+ * every queue launch has ended); -1 without a pool. */
+int lsbm_test_queue_pool_busy(int device);
 /* Testing / A/B: SSTable trailer batches (verify, dense trailer CRCs) as
  * equal-count pieces claimed by a workgroup's waves (1) or one range per wave
  * (0); -1 restores the default (LSBM_SST_PIECES, one range per wave). */

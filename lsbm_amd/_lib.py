@@ -20,6 +20,7 @@ LSBM_ERR_NO_DEVICE = -2
 LSBM_ERR_HIP = -3
 LSBM_ERR_NOMEM = -4
 LSBM_ERR_CORRUPTION = -5
+LSBM_ERR_QUEUE_FAULT = -6
 LSBM_CRC32C_MASKED = 0x1
 LSBM_CRC32C_MASK_DELTA = 0xA282EAD8
 LSBM_BLOCK_TRAILER_SIZE = 5
@@ -54,6 +55,10 @@ SIGNATURES = {
     "lsbm_test_fail_host_pipeline": (_int, [_int]),
     "lsbm_test_ragged_kernel": (_int, [_int]),
     "lsbm_test_fixed_queue": (_int, [_int]),
+    "lsbm_test_fixed_tail": (_int, [_int, _int]),
+    "lsbm_test_queue_fault": (_int, [_int, _int]),
+    "lsbm_test_queue_pool": (_int, [_int]),
+    "lsbm_test_queue_pool_busy": (_int, [_int]),
     "lsbm_test_sst_pieces": (_int, [_int]),
     "lsbm_host_threads": (_int, []),
     "lsbm_host_register": (_int, [ctypes.c_void_p, ctypes.c_uint64]),

@@ -31,7 +31,7 @@ namespace lsbm {
 hipError_t launch_fixed(const uint8_t* base, uint64_t stride, uint32_t rows, uint64_t n_blocks,
                         const uint32_t* init, uint32_t* out, uint32_t flags, uint32_t k_value,
                         const DevConsts* dc, int grid, hipStream_t stream,
-                        uint32_t* heads);
+                        uint32_t* heads, uint32_t own_rows, uint32_t* fault, uint32_t* done, uint32_t* busy);
 hipError_t launch_ragged(const RaggedArgs& a, int grid, hipStream_t stream);
 bool ragged_uses_stream(const RaggedArgs& a);
 int set_ragged_policy(int p);
@@ -69,8 +69,35 @@ struct DeviceState {
   int status = LSBM_ERR_NO_DEVICE;
   DevConsts* d_consts = nullptr;
   int num_cus = 0;
+  // The cross-XCC queue's sticky fault word: a wave that runs into the queue's
+  // spin cap drops its groups (crc32c_units.h WgQueue::cap_hit) and sets it;
+  // the results of that launch are wrong, and so may be the device's state, so
+  // every later call on the device fails (ensure_device).  Pinned host memory
+  // the kernels write directly (init_device); until the device is set up, and
+  // without one, the word is cap_local (lsbm_test_queue_fault sets either).
+  uint32_t cap_local = 0;
+  uint32_t* cap_word = &cap_local;
+  // The queue's head sets (take_head_set): kPoolSets sets of heads in device
+  // memory, zero whenever they are free, each with a busy word in pinned host
+  // memory (the same allocation as cap_word).  A launch takes a free set and
+  // marks it busy; its last workgroup out zeroes the heads again and clears
+  // the word (WgQueue::leave), so no launch waits for a memset in front of it
+  // (which cost a queue launch ~12 us of idle GPU between two kernels, more
+  // than the tail queue gains: DESIGN.md section 4).
+  std::mutex pool_mu;
+  uint32_t* pool = nullptr;       // kPoolRegions regions of heads, then kPoolSets done counters
+  uint32_t* pool_busy = nullptr;  // kPoolSets words
+  uint32_t pool_cursor = 0;
 };
+constexpr uint32_t kPoolRegions = 8;
+constexpr uint32_t kPoolSets = kPoolRegions * kQueueSetsPerRegion;
+constexpr uint32_t kPoolWords = kPoolRegions * kQueueWords + kPoolSets * kQueueDoneStride;
+constexpr uint32_t kPinnedBusyAt = 16;  // words: the busy words' offset from the fault word
 DeviceState g_dev[kMaxDevices];
+
+bool queue_faulted(const DeviceState* st) {
+  return __atomic_load_n(st->cap_word, __ATOMIC_RELAXED) != 0;
+}
 
 void build_consts(DevConsts* c) {
   gf2::byte_tables(gf2::byte_pow(kRowBytes), c->row_byte);
@@ -192,6 +219,27 @@ void init_device(int dev, DeviceState* st) {
     (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
   }
   (void)hipGetLastError();
+  uint32_t* w = nullptr;
+  e = hipHostMalloc(reinterpret_cast<void**>(&w), (kPinnedBusyAt + kPoolSets) * sizeof(uint32_t), hipHostMallocDefault);
+  if (e != hipSuccess || !w) {
+    st->status = fail_hip(e, "queue fault word");
+    hipFree(d);
+    hipSetDevice(prev);
+    return;
+  }
+  memset(w, 0, (kPinnedBusyAt + kPoolSets) * sizeof(uint32_t));
+  *w = st->cap_local;
+  st->cap_word = w;
+  // (no pool: every queue launch zeroes scratch heads of its own)
+  uint32_t* hpool = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&hpool), kPoolWords * sizeof(uint32_t)) == hipSuccess &&
+      hipMemset(hpool, 0, kPoolWords * sizeof(uint32_t)) == hipSuccess) {
+    st->pool = hpool;
+    st->pool_busy = w + kPinnedBusyAt;
+  } else {
+    if (hpool) (void)hipFree(hpool);
+    (void)hipGetLastError();
+  }
   st->d_consts = d;
   st->num_cus = cus;
   st->status = LSBM_OK;
@@ -201,14 +249,17 @@ void init_device(int dev, DeviceState* st) {
 int ensure_device(int dev, DeviceState** out) {
   if (dev < 0 || dev >= kMaxDevices) return fail(LSBM_ERR_NO_DEVICE, "bad device ordinal");
   DeviceState* st = &g_dev[dev];
+  const char* const faulted = "the cross-XCC queue hit its spin cap on this device: results were lost";
   if (!st->ready.load(std::memory_order_acquire)) {
     std::lock_guard<std::mutex> l(st->mu);
     if (!st->ready.load(std::memory_order_relaxed)) {
+      if (queue_faulted(st)) return fail(LSBM_ERR_QUEUE_FAULT, faulted);
       init_device(dev, st);
       if (st->status != LSBM_OK) return st->status;
       st->ready.store(true, std::memory_order_release);
     }
   }
+  if (queue_faulted(st)) return fail(LSBM_ERR_QUEUE_FAULT, faulted);
   *out = st;
   return LSBM_OK;
 }
@@ -230,25 +281,83 @@ uint64_t fixed_split_blocks() {
   return b;
 }
 
-// The fixed kernel's cross-XCC work queue (crc32c_units.h WgQueue), OFF by
-// default (LSBM_FIXED_QUEUE=1 or lsbm_test_fixed_queue: on).  It does what it
-// is for -- the eight XCDs' waves end within 5% of the launch instead of 14%
-// but the chip's aggregate read rate does not move (config 2 84.8% either
-// way, config 3 +0.7 points, a 10M-block shard -1 point; DESIGN.md section
-// 4): a statically split batch's fast XCDs finish early and the slow ones
-// then get their bandwidth.  Only for launches of at least 4 groups per wave,
-// and never while the stream is being captured into a graph (the heads are
-// per-call scratch).
-std::atomic<int> g_fixed_queue{-1};  // -1: not read yet; 0 off, 1 on (lsbm_test_fixed_queue)
-bool fixed_queue_on() {
+// The fixed kernel's schedule across XCDs (LSBM_FIXED_QUEUE, lsbm_test_fixed_queue):
+//   0  the static interleave: every XCD gets the same groups, and the XCDs that
+//      read faster (the even-numbered ones, ~8%) stand idle for the last ~12%
+//      of a launch;
+//   1  the full cross-XCC work queue (crc32c_units.h WgQueue, round 6): every
+//      row past the first is claimed at run time.  The XCDs then end together,
+//      but every batch of every workgroup pays for a claim; launches of at least
+//      kFullQueueMinRows rows (groups per wave);
+//   2  the tail queue (round 7, the default): the first K0 = rows - tail rows
+//      stay the static interleave's and only the last `tail` rows go through
+//      the queue (WgQueue own_rows), so that the XCDs that end their static
+//      rows first take the others' last groups.  Launches of at least
+//      kTailMinRows rows; tail = kTailSixteenths / 16 of the rows.
+// Measured in one process, alternating passes over config 2's buffer, 50
+// launches a pass (profiles/r07/tail_queue/): static
+// 631.8 us per launch; tails of 1/16, 1/8, 3/16 and 1/4 of the rows 622.2,
+// 620.3, 620.8 and 621.2 us; the full queue 626.5 us.  The slowest 1/8 pass
+// (621.7) beats the fastest static one (630.8): +1.9%.  Half of that comes from
+// the pooled heads (take_head_set): with per-call scratch heads and their
+// memset in front of every launch the same tail gained 0.9%.
+// Never while the stream is being captured into a graph (a replay would reuse
+// the capture's head set while another launch may hold it).
+constexpr int kFixedQueueDefault = 2;    // what -1 / no LSBM_FIXED_QUEUE means
+constexpr uint32_t kFullQueueMinRows = 4;  // mode 1
+constexpr uint32_t kTailMinRows = 8;       // mode 2
+constexpr uint32_t kTailSixteenths = 2;    // mode 2: tail = rows * kTailSixteenths / 16
+std::atomic<int> g_fixed_queue{-1};  // -1: not read yet; 0 static, 1 full queue, 2 tail queue (lsbm_test_fixed_queue)
+std::atomic<int> g_tail_min_rows{-1}, g_tail_rows{-1};  // lsbm_test_fixed_tail (-1: the constants above)
+int fixed_queue_mode() {
   int q = g_fixed_queue.load(std::memory_order_relaxed);
   if (q < 0) {
     const char* v = getenv("LSBM_FIXED_QUEUE");
-    q = (v && v[0] == '1') ? 1 : 0;
+    q = (v && v[0] >= '0' && v[0] <= '2' && v[1] == 0) ? v[0] - '0' : kFixedQueueDefault;
     int expect = -1;
     if (!g_fixed_queue.compare_exchange_strong(expect, q)) q = expect;
   }
-  return q == 1;
+  return q;
+}
+
+// A free head set of the device's pool, marked busy; -1: none (no pool, every
+// set in flight, or the pool switched off by lsbm_test_queue_pool).
+std::atomic<int> g_queue_pool{1};
+int take_head_set(DeviceState* st) {
+  if (!st->pool || !g_queue_pool.load(std::memory_order_relaxed)) return -1;
+  std::lock_guard<std::mutex> l(st->pool_mu);
+  for (uint32_t i = 0; i < kPoolSets; i++) {
+    const uint32_t s = (st->pool_cursor + i) % kPoolSets;
+    if (__atomic_load_n(st->pool_busy + s, __ATOMIC_ACQUIRE) == 0) {
+      __atomic_store_n(st->pool_busy + s, 1u, __ATOMIC_RELAXED);
+      st->pool_cursor = s + 1;
+      return (int)s;
+    }
+  }
+  return -1;
+}
+void release_head_set(DeviceState* st, int s) {  // (taken, never launched on)
+  __atomic_store_n(st->pool_busy + s, 0u, __ATOMIC_RELEASE);
+}
+uint32_t* set_heads(const DeviceState* st, int s) {
+  return st->pool + (size_t)(s / kQueueSetsPerRegion) * kQueueWords + (size_t)(s % kQueueSetsPerRegion) * 32u;
+}
+uint32_t* set_done(const DeviceState* st, int s) {
+  return st->pool + (size_t)kPoolRegions * kQueueWords + (size_t)s * kQueueDoneStride;
+}
+
+// The queue's late start for a launch of `ngroups` groups over `nwaves` waves:
+// K0 >= 1 static rows, or 0 for the static schedule (no queue).
+uint32_t fixed_own_rows(int mode, uint64_t ngroups, uint64_t nwaves) {
+  const uint64_t rows = (ngroups + nwaves - 1) / nwaves;
+  if (mode == 1) return ngroups >= kFullQueueMinRows * nwaves ? 1u : 0u;
+  if (mode != 2) return 0;
+  const int hook_min = g_tail_min_rows.load(std::memory_order_relaxed);
+  const int hook_tail = g_tail_rows.load(std::memory_order_relaxed);
+  const uint64_t min_rows = hook_min > 0 ? (uint64_t)hook_min : kTailMinRows;
+  if (ngroups < min_rows * nwaves || rows > 0xffffffull) return 0;
+  const uint64_t tail = hook_tail > 0 ? (uint64_t)hook_tail : std::max<uint64_t>(1, rows * kTailSixteenths / 16);
+  return (uint32_t)(rows > tail ? rows - tail : 1);
 }
 
 // SSTable trailer batches as claimed equal-count pieces (LSBM_SST_PIECES=1,
@@ -371,12 +480,51 @@ int run_ragged(RaggedArgs a, hipStream_t stream) {
 
 }  // namespace
 
-// Testing (include/lsbm_crc32c.h): the fixed kernel's cross-XCC queue on (1)
-// or off (0: the static interleave); -1 back to LSBM_FIXED_QUEUE's default.
+// Testing (include/lsbm_crc32c.h): the fixed kernel's schedule: 0 the static
+// interleave, 1 the full cross-XCC queue, 2 the tail queue; -1 back to
+// LSBM_FIXED_QUEUE's default.
 extern "C" __attribute__((visibility("default"))) int lsbm_test_fixed_queue(int on) {
-  if (on < -1 || on > 1) return -1;
+  if (on < -1 || on > 2) return -1;
   g_fixed_queue.store(on);
   return 0;
+}
+
+// Testing: the tail queue's minimum rows and tail rows (-1, -1: the defaults),
+// so that small batches reach the tail path.
+extern "C" __attribute__((visibility("default"))) int lsbm_test_fixed_tail(int min_rows, int tail_rows) {
+  if (min_rows < -1 || min_rows == 0 || tail_rows < -1 || tail_rows == 0) return -1;
+  g_tail_min_rows.store(min_rows);
+  g_tail_rows.store(tail_rows);
+  return 0;
+}
+
+// Testing / A/B: the queue's heads from the device's pool (1, the default) or
+// per-call scratch zeroed in stream order (0).
+extern "C" __attribute__((visibility("default"))) int lsbm_test_queue_pool(int on) {
+  if (on < 0 || on > 1) return -1;
+  g_queue_pool.store(on);
+  return 0;
+}
+
+// Testing: how many of the device's pooled head sets are busy (0 once every
+// queue launch has ended); -1 without a pool.
+extern "C" __attribute__((visibility("default"))) int lsbm_test_queue_pool_busy(int device) {
+  if (device < 0 || device >= kMaxDevices) return -1;
+  DeviceState* st = &g_dev[device];
+  if (!st->ready.load(std::memory_order_acquire) || !st->pool) return -1;
+  std::lock_guard<std::mutex> l(st->pool_mu);
+  int busy = 0;
+  for (uint32_t i = 0; i < kPoolSets; i++) busy += __atomic_load_n(st->pool_busy + i, __ATOMIC_ACQUIRE) != 0;
+  return busy;
+}
+
+// Testing: set (1) or clear (0) the device's sticky queue-fault word, as a
+// wave that hit the queue's spin cap would; returns the word's value before.
+extern "C" __attribute__((visibility("default"))) int lsbm_test_queue_fault(int device, int value) {
+  if (device < 0 || device >= kMaxDevices || value < 0 || value > 1) return -1;
+  DeviceState* st = &g_dev[device];
+  std::lock_guard<std::mutex> l(st->mu);
+  return (int)__atomic_exchange_n(st->cap_word, (uint32_t)value, __ATOMIC_RELAXED);
 }
 
 // Testing (include/lsbm_crc32c.h): SSTable trailer pieces on (1) or off (0);
@@ -434,6 +582,14 @@ __attribute__((visibility("default"))) int lsbm_crc32c_shutdown(void) {
     (void)hipDeviceSynchronize();  // no kernel may still read the tables
     if (st->d_consts) (void)hipFree(st->d_consts);
     st->d_consts = nullptr;
+    if (st->pool) (void)hipFree(st->pool);
+    st->pool = nullptr;
+    st->pool_busy = nullptr;
+    if (st->cap_word != &st->cap_local) {  // (a fault outlives the shutdown)
+      st->cap_local = *st->cap_word;
+      (void)hipHostFree(st->cap_word);
+      st->cap_word = &st->cap_local;
+    }
     st->status = LSBM_ERR_NO_DEVICE;
     st->ready.store(false);
   }
@@ -474,25 +630,43 @@ __attribute__((visibility("default"))) int lsbm_crc32c_fixed_dev(
     uint32_t* heads = nullptr;
     const uint64_t nwaves = (uint64_t)st->num_cus * kWavesPerWg;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (fixed_queue_on() && (min_m + 7) / 8 >= 4 * nwaves && hipStreamIsCapturing(hs, &cap) == hipSuccess &&
+    // (every launch by the smallest one's rule: one decision per call)
+    const int qmode = fixed_queue_mode();
+    std::vector<int> sets;  // pooled head sets, one per launch
+    if (fixed_own_rows(qmode, (min_m + 7) / 8, nwaves) != 0 && hipStreamIsCapturing(hs, &cap) == hipSuccess &&
         cap == hipStreamCaptureStatusNone) {
-      const size_t bytes = launches * kQueueWords * sizeof(uint32_t);
-      if (hipMallocAsync(reinterpret_cast<void**>(&heads), bytes, hs) != hipSuccess) {
-        (void)hipGetLastError();
-        heads = nullptr;
-      } else if (hipMemsetAsync(heads, 0, bytes, hs) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFreeAsync(heads, hs);
-        heads = nullptr;
+      for (uint64_t i = 0; i < launches; i++) {
+        const int sidx = take_head_set(st);
+        if (sidx < 0) break;
+        sets.push_back(sidx);
+      }
+      if (sets.size() != launches) {  // no pool, or not enough free sets: scratch heads, zeroed in stream order
+        for (int sidx : sets) release_head_set(st, sidx);
+        sets.clear();
+        const size_t bytes = launches * kQueueWords * sizeof(uint32_t);
+        if (hipMallocAsync(reinterpret_cast<void**>(&heads), bytes, hs) != hipSuccess) {
+          (void)hipGetLastError();
+          heads = nullptr;
+        } else if (hipMemsetAsync(heads, 0, bytes, hs) != hipSuccess) {
+          (void)hipGetLastError();
+          (void)hipFreeAsync(heads, hs);
+          heads = nullptr;
+        }
       }
     }
     hipError_t e = hipSuccess;
     uint64_t li = 0;
     for (uint64_t f = 0; f < n_blocks && e == hipSuccess; li++) {
       const uint64_t m = (per && n_blocks - f >= 2 * per) ? per : n_blocks - f;
+      const bool pooled = !sets.empty();
+      uint32_t* const h = pooled ? set_heads(st, sets[li]) : heads ? heads + li * kQueueWords : nullptr;
       e = launch_fixed(static_cast<const uint8_t*>(d_base) + f * stride, stride,
                        (uint32_t)(len / kRowBytes), m, d_init ? d_init + f : nullptr, d_out + f, flags,
-                       k_value, st->d_consts, grid_for(st, m), hs, heads ? heads + li * kQueueWords : nullptr);
+                       k_value, st->d_consts, grid_for(st, m), hs, h,
+                       h ? fixed_own_rows(qmode, (m + 7) / 8, nwaves) : 1u, st->cap_word,
+                       pooled ? set_done(st, sets[li]) : nullptr, pooled ? st->pool_busy + sets[li] : nullptr);
+      if (e != hipSuccess && pooled)  // (this launch's set and the later ones': never launched on)
+        for (uint64_t k = li; k < launches; k++) release_head_set(st, sets[k]);
       f += m;
     }
     if (heads) (void)hipFreeAsync(heads, hs);

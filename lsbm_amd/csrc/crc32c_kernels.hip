@@ -71,7 +71,10 @@ __global__ __launch_bounds__(kBlockThreads) void crc32c_fixed_kernel(
     const uint8_t* __restrict__ base, uint64_t stride, uint32_t rows_arg, uint64_t n_blocks,
     const uint32_t* __restrict__ init, uint32_t* __restrict__ out, uint32_t flags,
     uint32_t k_value /* A^len(~0) ^ ~0: the init term of crc32c::Value */,
-    const DevConsts* __restrict__ dc, uint32_t* __restrict__ heads /* null: no cross-XCC queue */) {
+    const DevConsts* __restrict__ dc, uint32_t* __restrict__ heads /* null: no cross-XCC queue */,
+    uint32_t own_rows /* the queue's late start: static rows before its items, >= 1 */,
+    uint32_t* __restrict__ fault /* the queue's sticky spin-cap word */,
+    uint32_t* __restrict__ done, uint32_t* __restrict__ busy /* pooled heads: handed back zeroed (WgQueue::leave) */) {
   const uint32_t rows = kRows ? kRows : rows_arg;  // kRows != 0: fully unrolled
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t g = lane >> 3, li = lane & 7u;
@@ -128,11 +131,15 @@ __global__ __launch_bounds__(kBlockThreads) void crc32c_fixed_kernel(
 #else
   auto next_grp = [&](uint64_t gp) -> uint64_t { return gp + nwaves; };
 #endif
-  // With the cross-XCC queue (crc32c_units.h): row 0 is the waves' own, the
-  // rest comes in workgroup batches of W groups (items) from the heads.
+  // With the cross-XCC queue (crc32c_units.h): the first own_rows rows are the
+  // static interleave's (row 0 the waves' own, the others taken in turn as
+  // above), the rest comes in workgroup batches of W groups (items) from the
+  // heads.
   __shared__ uint32_t s_wq[kWqWords];
+  const uint64_t own_groups = (uint64_t)own_rows * nwaves;
   const WgQueue<kWavesPerWg> wq{heads, (lds_u32*)s_wq,
-                                ngroups > nwaves ? (ngroups - nwaves + kWavesPerWg - 1) / kWavesPerWg : 0};
+                                ngroups > own_groups ? (ngroups - own_groups + kWavesPerWg - 1) / kWavesPerWg : 0,
+                                own_rows, fault};
   if (heads && threadIdx.x == 0) wq.init(xcc_id());  // (ordered by load_lds_tables' barrier)
 
   uint64_t grp = wave;
@@ -147,7 +154,8 @@ __global__ __launch_bounds__(kBlockThreads) void crc32c_fixed_kernel(
   load_lds_tables(g_lds, dc);
   DIAG_STAMP(1);
 
-  uint32_t pend_pub = heads && wave_in_wg == 0 ? kWqLead : 0u;  // a batch this wave publishes
+  // a batch this wave publishes: batch 1 by the taker of slot 0 of row own_rows - 1
+  uint32_t pend_pub = heads && wave_in_wg == 0 && own_rows == 1 ? kWqLead : 0u;
   for (;;) {
     if (grp < ngroups) {
       const uint64_t blk = grp * 8 + g;
@@ -202,16 +210,25 @@ __global__ __launch_bounds__(kBlockThreads) void crc32c_fixed_kernel(
       if (grp >= ngroups) break;
       continue;
     }
-    // the next slot: wave-group `slot` of batch `bt`
-    const uint32_t k = wq.take(), bt = k / kWavesPerWg, slot = k % kWavesPerWg;
+    // the next slot: a static row's (a group past the batch's end is skipped:
+    // the wave goes on to the queue's first batch, which ends it), or
+    // wave-group `slot` of batch `bt`
+    const uint32_t k = wq.take(), slot = k % kWavesPerWg;
+    if (k < own_rows * kWavesPerWg) {
+      if (k == (own_rows - 1) * kWavesPerWg) pend_pub = kWqLead;
+      grp = (uint64_t)(k / kWavesPerWg) * nwaves + (uint64_t)blockIdx.x * kWavesPerWg + slot;
+      continue;
+    }
+    const uint32_t bt = k / kWavesPerWg - own_rows + 1;
     if (slot == 0) pend_pub = bt + kWqLead;
     const uint32_t it = wq.read(bt);
     if (it == kWqNone) {
       if (pend_pub) wq.publish(pend_pub);  // (kWqNone as well; no wave of this workgroup waits for it)
       break;
     }
-    grp = nwaves + (uint64_t)it * kWavesPerWg + slot;  // (past ngroups in the last item: a slot without a group)
+    grp = own_groups + (uint64_t)it * kWavesPerWg + slot;  // (past ngroups in the last item: a slot without a group)
   }
+  if (heads) wq.leave(done, busy);
   DIAG_STAMP(2);
   DIAG_XCC_W(wave);
 }
@@ -421,10 +438,11 @@ __global__ __launch_bounds__(kBlockThreads) void stream_read_kernel(const uint8_
 // ---- host-callable launchers (C++ linkage, used by crc32c_engine.cc) ----
 hipError_t launch_fixed(const uint8_t* base, uint64_t stride, uint32_t rows, uint64_t n_blocks,
                         const uint32_t* init, uint32_t* out, uint32_t flags, uint32_t k_value,
-                        const DevConsts* dc, int grid, hipStream_t stream, uint32_t* heads) {
+                        const DevConsts* dc, int grid, hipStream_t stream, uint32_t* heads, uint32_t own_rows,
+                        uint32_t* fault, uint32_t* done, uint32_t* busy) {
 #define LSBM_LAUNCH_FIXED(HI, R)                                                        \
   hipLaunchKernelGGL((crc32c_fixed_kernel<HI, R>), dim3(grid), dim3(kBlockThreads), 0, stream, \
-                     base, stride, rows, n_blocks, init, out, flags, k_value, dc, heads)
+                     base, stride, rows, n_blocks, init, out, flags, k_value, dc, heads, own_rows, fault, done, busy)
   // compile-time row counts for the SSTable-sized configs: 4 KiB and 64 KiB
   if (init) {
     if (rows == 32) LSBM_LAUNCH_FIXED(true, 32);

@@ -73,14 +73,23 @@ constexpr uint32_t kLdsWords = kLdsBytes / 4;
 // fails this assert rather than hipcc's LDS limit on some kernel.
 constexpr uint32_t kLdsKernelWords = 20;  // (fixed kernel: s_next and the WgQueue words)
 
-// The cross-XCC work queue's heads (crc32c_units.h): one word per XCC, each
-// on its own 64-B line; kQueueWords words of scratch per launch.
+// The cross-XCC work queue's heads (crc32c_units.h): one word per XCC, 4,160 B
+// apart, so that the eight heads' atomics go to different memory channels
+// (heads on neighbouring 64-B lines, stride 16: the full queue 1.8% slower than
+// the static schedule instead of 0.2%, and no tail gained; round 6 measured the
+// same, profiles/r06/queue/README.md).  kQueueWords words per launch.
+// Head sets that outlive a launch (crc32c_engine.cc's pool) are interleaved:
+// kQueueSetsPerRegion sets share one region of kQueueWords words, set s at word
+// 32 s of it (128 B apart), and each set has a counter of the workgroups that
+// have left, in an array behind the regions (kQueueDoneStride words apart).
 #ifndef LSBM_QUEUE_STRIDE  // (A/B builds override)
-#define LSBM_QUEUE_STRIDE 16
+#define LSBM_QUEUE_STRIDE 1040
 #endif
 constexpr uint32_t kQueueHeads = 8;
 constexpr uint32_t kQueueStride = LSBM_QUEUE_STRIDE;
 constexpr uint32_t kQueueWords = kQueueHeads * kQueueStride;
+constexpr uint32_t kQueueSetsPerRegion = kQueueStride >= 64 ? kQueueStride / 32 : 1;
+constexpr uint32_t kQueueDoneStride = 32;
 static_assert(kLdsBytes % 16 == 0 && kLdsBytes + 4u * kLdsKernelWords <= 160u * 1024u,
               "one LDS image per CU, plus the kernels' work counters");
 static_assert(kStreamHM % 16 == 0, "ds_read_b128 of a mask");

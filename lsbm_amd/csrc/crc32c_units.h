@@ -41,7 +41,17 @@ __shared__ uint32_t g_lds[kLdsWords];
 // every claimed item is processed; entry x % kRing is reused only once all W
 // readers of batch x - kRing have read it.  No wait can form a cycle (each
 // waits only on smaller batches), and every spin is capped (kSpinCap): a
-// protocol fault gives wrong results, which the tests see, never a hang.
+// protocol fault gives wrong results, which the tests see, never a hang, and
+// sets the sticky word `fault` (pinned host memory; the engine then refuses
+// every later call on the device, crc32c_engine.cc).
+// Late start (round 7, own_rows = K0 >= 1): the first K0 rows of the batch stay
+// the static interleave's -- slot k < K0 W of a workgroup is group
+// (k / W) nwaves + W blockIdx + k % W, with no global traffic, no ring and no
+// publication -- and only the groups from K0 nwaves on are queue items: slot
+// k >= K0 W is wave-group k % W of batch k / W - K0 + 1, item `it` covers the
+// groups K0 nwaves + it W + [0, W).  Batch 1 is published by the wave that
+// takes slot 0 of row K0 - 1 (K0 = 1: wave 0, at its own first group: round
+// 6's full queue).  tests/test_queue_tail_schedule.py restates this.
 // ---------------------------------------------------------------------------
 // (kQueueHeads, kQueueStride, kQueueWords: crc32c_types.h)
 
@@ -59,7 +69,7 @@ __device__ __forceinline__ uint32_t queue_take(uint32_t* heads, uint32_t h) {
 }
 
 constexpr uint32_t kWqRing = 4, kWqLead = 1, kWqNone = 0xffffffffu, kSpinCap = 1u << 20;
-constexpr uint32_t kWqWords = 3 + 3 * kWqRing;  // next, head, exhausted, tag[R], item[R], read[R]
+constexpr uint32_t kWqWords = 4 + 3 * kWqRing;  // next, head, exhausted, tag[R], item[R], read[R], left
 static_assert(kWqLead == 1, "wave 0 publishes batch 1 only: the batches before the first slot-0 taker's");
 static_assert(kWqRing > kWqLead, "an entry is reused only after its batch's slots were all taken");
 
@@ -70,9 +80,11 @@ typedef __attribute__((address_space(3))) uint32_t lds_u32;
 
 template <uint32_t W>
 struct WgQueue {
-  uint32_t* heads;  // global heads
-  lds_u32* s;       // LDS words (kWqWords)
-  uint64_t items;   // items the heads hand out
+  uint32_t* heads;    // global heads
+  lds_u32* s;         // LDS words (kWqWords)
+  uint64_t items;     // items the heads hand out
+  uint32_t own_rows;  // K0: rows of the static interleave before the queue's items (wave-uniform, >= 1)
+  uint32_t* fault;    // sticky word set when a spin hits kSpinCap (null: none)
 
   __device__ __forceinline__ volatile lds_u32* v(uint32_t i) const { return (volatile lds_u32*)(s + i); }
   // (thread 0, before a workgroup barrier)
@@ -80,6 +92,7 @@ struct WgQueue {
     *v(0) = W;  // slots 0 .. W-1: row 0, the waves' own
     *v(1) = xcc;
     *v(2) = 0;
+    *v(3 + 3 * kWqRing) = 0;
     for (uint32_t e = 0; e < kWqRing; e++) {
       *v(3 + e) = 0;  // (tag 0: batch 0, which is never read)
       *v(3 + kWqRing + e) = kWqNone;
@@ -92,6 +105,12 @@ struct WgQueue {
     return __builtin_amdgcn_readfirstlane(k);
   }
   __device__ __forceinline__ uint32_t rd(uint32_t i) const { return __builtin_amdgcn_readfirstlane(*v(i)); }
+  // A spin ran into kSpinCap: this wave's groups are lost, say so (a plain
+  // vector store of lane 0 to host memory; cold path).
+  __device__ __forceinline__ void cap_hit() const {
+    if ((threadIdx.x & 63u) == 0 && fault)
+      __hip_atomic_store(fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
   // Claim batch x's item from the heads and publish it (wave-uniform).
   __device__ __forceinline__ void publish(uint32_t x) const {
     const uint32_t e = x % kWqRing, pe = (x - 1) % kWqRing;
@@ -109,6 +128,7 @@ struct WgQueue {
       }
       if (++out < kQueueHeads) h = (h + 1) & (kQueueHeads - 1);
     }
+    if (spins >= kSpinCap) cap_hit();
     if ((threadIdx.x & 63u) == 0) {  // (LDS ops of one wave complete in order: item before tag)
       *v(1) = h;
       *v(2) = out;
@@ -117,13 +137,34 @@ struct WgQueue {
       *v(3 + e) = x;
     }
   }
+  // A wave is done with the queue (every wave of the launch calls this once,
+  // after its last claim has returned).  Heads from the engine's pool (done,
+  // busy non-null) are handed back zeroed: the last wave out of a workgroup
+  // counts the workgroup in *done, and the last workgroup out of the launch
+  // zeroes the heads and the counter and then clears the set's busy word in
+  // pinned host memory (release, system scope: whoever sees it clear may launch
+  // on these heads at once, on any stream).  One global atomic per workgroup,
+  // behind its last row.
+  __device__ __forceinline__ void leave(uint32_t* done, uint32_t* busy) const {
+    if (!done || (threadIdx.x & 63u) != 0) return;
+    if (__atomic_fetch_add(s + 3 + 3 * kWqRing, 1u, __ATOMIC_RELAXED) != W - 1) return;
+    if (__hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != gridDim.x - 1) return;
+    for (uint32_t h = 0; h < kQueueHeads; h++)
+      __hip_atomic_store(heads + h * kQueueStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(busy, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
   // Batch b's item (kWqNone: the queue is exhausted), counted as read.
   __device__ __forceinline__ uint32_t read(uint32_t b) const {
     const uint32_t e = b % kWqRing;
     uint32_t spins = 0;
     while (rd(3 + e) != b)
-      if (++spins >= kSpinCap) return kWqNone;
-      else __builtin_amdgcn_s_sleep(2);
+      if (++spins >= kSpinCap) {
+        cap_hit();
+        return kWqNone;
+      } else {
+        __builtin_amdgcn_s_sleep(2);
+      }
     const uint32_t it = rd(3 + kWqRing + e);
     if ((threadIdx.x & 63u) == 0) __atomic_fetch_add(s + 3 + 2 * kWqRing + e, 1u, __ATOMIC_RELAXED);
     return it;
