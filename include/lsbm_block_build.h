@@ -62,6 +62,13 @@ extern "C" {
 #define LSBM_BUILD_BAD_INPUT 2u
 #define LSBM_BUILD_TOO_LARGE 3u
 
+/* Per-run status of the compaction merge that feeds the builder
+ * (include/lsbm_merge.h, which says what each means). */
+#define LSBM_MERGE_OK 0u
+#define LSBM_MERGE_NO_ROOM 1u
+#define LSBM_MERGE_BAD_INPUT 2u
+#define LSBM_MERGE_UNSORTED 3u
+
 /* Device scratch lsbm_block_plan_dev needs for n_entries entries in n_tables
  * tables (bytes; the caller allocates, contents are the call's own). */
 uint64_t lsbm_block_plan_scratch_bytes(uint64_t n_entries, uint64_t n_tables);

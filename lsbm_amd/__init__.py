@@ -9,12 +9,14 @@
   lsbm_amd.block    SSTable block reader: batched Block::Iter scan / decode / Seek, Table::InternalGet
   lsbm_amd.block_build  SSTable block builder: batched flush plan, BlockBuilder Add / Finish, index
                     blocks, whole table files
+  lsbm_amd.merge    compaction merge: batched MergingIterator over sorted runs, DoCompactionWork's
+                    drop rule and output-file cut, input table images -> output table files
 
 The compute lives in lsbm_amd/liblsbm_crc32c.so (hand-written gfx950 HIP
 kernels behind the C ABIs in include/lsbm_crc32c.h, include/lsbm_bloom.h, include/lsbm_snappy.h and
-include/lsbm_block.h, include/lsbm_block_build.h).
+include/lsbm_block.h, include/lsbm_block_build.h, include/lsbm_merge.h).
 """
 from ._lib import LIB_PATH, LsbmError, lib  # noqa: F401
 
 __all__ = ["LIB_PATH", "LsbmError", "lib", "crc32c", "engine", "table", "log", "bloom", "snappy",
-           "block", "block_build"]
+           "block", "block_build", "merge"]

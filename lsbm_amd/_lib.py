@@ -113,6 +113,14 @@ BLOCK_BUILD_SIGNATURES = {
     "lsbm_index_block_build_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _int, _vp, _u64,
                                           _vp, _vp, _vp, _vp]),
 }
+# every symbol include/lsbm_merge.h declares
+MERGE_SIGNATURES = {
+    "lsbm_merge_scratch_bytes": (_u64, [_u64, _u64]),
+    "lsbm_merge_plan_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _int, _u32, _u64, _vp, _vp, _vp, _vp, _vp,
+                                   _u64, _vp]),
+    "lsbm_merge_gather_dev": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp,
+                                     _vp]),
+}
 
 _lib = None
 
@@ -134,7 +142,7 @@ def lib():
                 "There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(BLOCK_SIGNATURES.items())
-                                  + list(BLOCK_BUILD_SIGNATURES.items())):
+                                  + list(BLOCK_BUILD_SIGNATURES.items()) + list(MERGE_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)
