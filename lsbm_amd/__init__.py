@@ -11,12 +11,14 @@
                     blocks, whole table files
   lsbm_amd.merge    compaction merge: batched MergingIterator over sorted runs, DoCompactionWork's
                     drop rule and output-file cut, input table images -> output table files
+  lsbm_amd.sstable  tables with snappy-compressed blocks: WriteBlock's keep rule and block packing,
+                    batched ReadBlock, table writer, Get and compaction over either block type
 
 The compute lives in lsbm_amd/liblsbm_crc32c.so (hand-written gfx950 HIP
 kernels behind the C ABIs in include/lsbm_crc32c.h, include/lsbm_bloom.h, include/lsbm_snappy.h and
-include/lsbm_block.h, include/lsbm_block_build.h, include/lsbm_merge.h).
+include/lsbm_block.h, include/lsbm_block_build.h, include/lsbm_merge.h, include/lsbm_table_pack.h).
 """
 from ._lib import LIB_PATH, LsbmError, lib  # noqa: F401
 
 __all__ = ["LIB_PATH", "LsbmError", "lib", "crc32c", "engine", "table", "log", "bloom", "snappy",
-           "block", "block_build", "merge"]
+           "block", "block_build", "merge", "sstable"]

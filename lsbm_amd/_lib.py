@@ -122,6 +122,14 @@ MERGE_SIGNATURES = {
                                      _vp]),
 }
 
+# every symbol include/lsbm_table_pack.h declares
+TABLE_PACK_SIGNATURES = {
+    "lsbm_block_pack_scratch_bytes": (_u64, [_u64]),
+    "lsbm_block_pack_plan_dev": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "lsbm_block_pack_dev": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _u64,
+                                   _vp]),
+}
+
 _lib = None
 
 
@@ -142,7 +150,8 @@ def lib():
                 "There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(BLOCK_SIGNATURES.items())
-                                  + list(BLOCK_BUILD_SIGNATURES.items()) + list(MERGE_SIGNATURES.items())):
+                                  + list(BLOCK_BUILD_SIGNATURES.items()) + list(MERGE_SIGNATURES.items())
+                                  + list(TABLE_PACK_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)

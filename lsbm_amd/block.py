@@ -181,8 +181,9 @@ def table_get(image, index_handle, keys, key_offsets, filter=None, verify=True, 
     and value {offset, length}; SEEK_NOT_VALID when the index or the data block
     has no entry at or after the key; SEEK_BAD_* from either Seek;
     GET_FILTERED; GET_BAD_CHECKSUM; GET_BAD_TYPE; GET_NEEDS_UNCOMPRESS for a
-    block that is not kNoCompression.  As in the reference the caller compares
-    the found key's user key with its own (SaveValue)."""
+    block that is not kNoCompression (sstable.table_get reads tables of either
+    block type).  As in the reference the caller compares the found key's user
+    key with its own (SaveValue)."""
     torch = _torch()
     from . import bloom, table
     if stream is not None:  # (the masking between the steps is torch's: on the same stream)

@@ -182,7 +182,8 @@ def table_build(keys, key_offsets, values, value_image, cmp=INTERNAL_KEY, block_
     """TableBuilder (table/table_builder.cc) Add for every entry, then Finish,
     for one complete table file: data blocks, the filter block
     (BloomFilterPolicy(bits_per_key); InternalFilterPolicy under INTERNAL_KEY),
-    the metaindex block, the index block, every trailer and the footer.
+    the metaindex block, the index block, every trailer and the footer
+    (kNoCompression only; sstable.write_table writes snappy-compressed tables).
     Returns (file_image uint8 device tensor, data_handles int64 device tensor of
     {offset, size} pairs, index_handle (offset, size))."""
     torch = _torch()

@@ -222,7 +222,7 @@ def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None
             smallest_snapshot=None, bottom_level=False, block_size=4096, restart_interval=16, bits_per_key=None,
             stream=None):
     """The table-to-table part of DoCompactionWork for device-resident
-    kNoCompression tables: images[t] is input table t's file image and
+    kNoCompression tables (sstable.compact: either block type): images[t] is input table t's file image and
     data_handles[t] its data blocks' {offset, size} pairs (or index_handles[t]
     its index block's (offset, size), from which they are read).  Input t is
     run t of the merge, so list the inputs as the reference's MergingIterator

@@ -1,0 +1,627 @@
+"""SSTables with either block type (kNoCompression / kSnappyCompression) on the
+GPU: TableBuilder::WriteBlock's keep rule and ReadBlock's type switch of lsbm's
+table/ layer, and the table writer, Get and compaction built on them.
+
+Thin wrappers over include/lsbm_table_pack.h and the other modules.  Device
+tensors in, device tensors out; every call enqueues on `stream` (default:
+torch's current stream).
+
+    pack_plan(raw_len, comp_len, ...)  the keep rule (table/table_builder.cc:187)
+                                       and the offsets that follow from it
+    pack(raw, raw_handles, comp, comp_offsets, types, handles, out, ...)
+                                       every block, raw or compressed, moved to
+                                       its final offset
+    read_blocks(image, handles, ...)   batched ReadBlock (table/format.cc:66-148)
+    write_table(keys, key_offsets, values, value_image, ...)
+                                       TableBuilder with WriteBlock's rule on the
+                                       data, metaindex and index blocks
+    table_get(image, index_handle, keys, key_offsets, ...)
+                                       Table::InternalGet over either block type
+    compact(images, ...)               merge.compact over either block type
+
+Handles are int64 {offset, size} pairs.  block.table_get, block_build.table_build
+and merge.compact keep their kNoCompression-only behaviour.
+"""
+from collections import namedtuple
+
+import numpy as np
+
+from ._lib import check, lib
+from .block import (BYTEWISE, GET_BAD_CHECKSUM, GET_BAD_TYPE, GET_FILTERED, INTERNAL_KEY, SEEK_BAD_HANDLE,
+                    SEEK_VALID)
+from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .merge import OutputTable
+from .table import kBlockTrailerSize, kNoCompression, kSnappyCompression, seal_blocks
+
+# per-block status of pack (include/lsbm_block_build.h)
+PACK_OK = 0
+PACK_NO_ROOM = 1
+PACK_BAD_INPUT = 2
+
+# per-block status of read_blocks (include/lsbm_table_pack.h), in ReadBlock's order
+READ_OK = 0
+READ_TRUNCATED = 1        # Corruption("truncated block read")
+READ_BAD_CHECKSUM = 2     # Corruption("block checksum mismatch")
+READ_BAD_COMPRESSED = 3   # Corruption("corrupted compressed block contents")
+READ_BAD_TYPE = 4         # Corruption("bad block type")
+READ_TOO_LARGE = 5        # the preambles ask for more than max_bytes (no reference verdict)
+
+READ_MESSAGE = {READ_TRUNCATED: "truncated block read", READ_BAD_CHECKSUM: "block checksum mismatch",
+                READ_BAD_COMPRESSED: "corrupted compressed block contents", READ_BAD_TYPE: "bad block type",
+                READ_TOO_LARGE: "compressed blocks ask for more than max_bytes"}
+
+# table_get: block.table_get's states (GET_NEEDS_UNCOMPRESS never appears) and
+GET_BAD_COMPRESSED = 9    # the data block does not uncompress, or is READ_TOO_LARGE
+
+COMP_NONE = -1            # comp_len of a block that could not be compressed (UINT64_MAX)
+
+GetResult = namedtuple("GetResult", "state key_len value data_handle value_image")
+# data blocks built (and compressed) once, for write_table's second half
+_Blocks = namedtuple("_Blocks", "raw raw_handles comp comp_offsets comp_len")
+
+
+def _i64(t, name):
+    torch = _torch()
+    if t.dtype != torch.int64 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous int64 tensor")
+
+
+def _u8(t, name):
+    torch = _torch()
+    if t.dtype != torch.uint8 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous uint8 tensor")
+
+
+def _scratch(n, dev):
+    torch = _torch()
+    nbytes = int(lib().lsbm_block_pack_scratch_bytes(n))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+
+
+def keep_compressed(raw_len, comp_len):
+    """WriteBlock's rule as lsbm_block_pack_plan_dev evaluates it: unsigned
+    64-bit arithmetic, COMP_NONE (UINT64_MAX) never kept."""
+    mask = (1 << 64) - 1
+    raw_len, comp_len = int(raw_len) & mask, int(comp_len) & mask
+    return comp_len != mask and comp_len < ((raw_len - raw_len // 8) & mask)
+
+
+def pack_plan(raw_len, comp_len=None, first_offset=0, gap=kBlockTrailerSize, stream=None):
+    """(types uint8[n], handles int64[2n], end int64[1]): type[i] = 1 where the
+    compressed form is kept (comp_len[i] < raw_len[i] - raw_len[i] / 8; comp_len
+    None: nowhere), size[i] the kept form's, offset[i] = first_offset + the
+    sizes and gaps before it, end = the offset after the last block's gap."""
+    torch = _torch()
+    _require_cuda(raw_len, comp_len)
+    _i64(raw_len, "raw_len")
+    n = raw_len.numel()
+    if comp_len is not None:
+        _i64(comp_len, "comp_len")
+        if comp_len.numel() != n:
+            raise ValueError("comp_len needs one entry per block")
+    dev = raw_len.device
+    types = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)[:n]
+    handles = torch.zeros(max(2 * n, 1), dtype=torch.int64, device=dev)[:2 * n]
+    end = torch.zeros(1, dtype=torch.int64, device=dev)
+    scratch = _scratch(n, dev)
+    check(lib().lsbm_block_pack_plan_dev(_ptr(raw_len), _ptr(comp_len), n, int(first_offset), int(gap),
+                                         _ptr(types), _ptr(handles), _ptr(end), _ptr(scratch),
+                                         scratch.numel() * 8, _stream_ptr(stream)), "lsbm_block_pack_plan_dev")
+    return types, handles, end
+
+
+def pack(raw, raw_handles, comp, comp_offsets, types, handles, out, gap=kBlockTrailerSize, stream=None):
+    """Block i: handles[2i+1] bytes to out[handles[2i]:], from raw[raw_handles[2i]:]
+    where types[i] == 0 and from comp[comp_offsets[i]:] where it is 1 (comp /
+    comp_offsets may be None when no block is).  Returns status int32[n]."""
+    torch = _torch()
+    _require_cuda(raw, raw_handles, comp, comp_offsets, types, handles, out)
+    _u8(out, "out")
+    _u8(types, "types")
+    _i64(handles, "handles")
+    for t, name, chk in ((raw, "raw", _u8), (comp, "comp", _u8), (raw_handles, "raw_handles", _i64),
+                         (comp_offsets, "comp_offsets", _i64)):
+        if t is not None:
+            chk(t, name)
+    n = types.numel()
+    if handles.numel() != 2 * n or (raw_handles is not None and raw_handles.numel() != 2 * n) or \
+            (comp_offsets is not None and comp_offsets.numel() != n):
+        raise ValueError("handles / raw_handles need one pair, comp_offsets one entry per block")
+    dev = out.device
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    scratch = _scratch(n, dev)
+    check(lib().lsbm_block_pack_dev(_ptr(raw), raw.numel() if raw is not None else 0, _ptr(raw_handles),
+                                    _ptr(comp), comp.numel() if comp is not None else 0, _ptr(comp_offsets),
+                                    _ptr(types), _ptr(handles), n, int(gap), _ptr(out), out.numel(),
+                                    _ptr(status), _ptr(scratch), scratch.numel() * 8, _stream_ptr(stream)),
+          "lsbm_block_pack_dev")
+    return status
+
+
+def _preamble(image, off, size):
+    """snappy::GetUncompressedLength of the blocks at off (int64 tensors; only
+    where size >= 0 and the block is inside the image): (ulen, ok), with torch
+    ops so that the contents image is sized without a read of its own."""
+    torch = _torch()
+    ulen = torch.zeros_like(off)
+    done = torch.zeros_like(off, dtype=torch.bool)
+    ok = torch.zeros_like(off, dtype=torch.bool)
+    for i in range(5):
+        have = ~done & (size > i)
+        b = image[torch.where(have, off + i, torch.zeros_like(off))].to(torch.int64)
+        bad = have & (b >= 16) if i == 4 else torch.zeros_like(have)
+        have = have & ~bad
+        ulen = torch.where(have, ulen | ((b & 127) << (7 * i)), ulen)
+        last = have & (b < 128)
+        ok = ok | last
+        done = done | last | bad | ~have
+    return torch.where(ok, ulen, torch.zeros_like(ulen)), ok
+
+
+def read_blocks(image, handles, verify=True, max_bytes=1 << 30, stream=None):
+    """Batched ReadBlock (table/format.cc:66-148) of the blocks `handles` names
+    in the file image, in the reference's order of checks: the handle plus its
+    trailer inside the image (READ_TRUNCATED), the trailer's CRC when `verify`
+    (READ_BAD_CHECKSUM), then the type byte: kNoCompression, the bytes as they
+    are; kSnappyCompression, GetUncompressedLength and RawUncompress
+    (READ_BAD_COMPRESSED when either fails); anything else READ_BAD_TYPE.
+    READ_TOO_LARGE (no reference verdict): a compressed block whose preamble
+    alone asks for more than max_bytes, and of the others every one at which
+    the running sum of the preambles passes max_bytes; nothing is allocated
+    for them.
+
+    Returns (contents uint8, out_handles int64[2n], status int32[n]): block i's
+    contents are contents[out_handles[2i], + out_handles[2i+1]); a failed block
+    has size 0.  contents holds the snappy blocks' outputs, uncompressed
+    straight into their places, then the raw blocks, moved by pack, back to back
+    (a snappy block that fails in RawUncompress leaves its place unused).  The
+    host reads one pair of numbers: the sizes of contents and of the staging of
+    the compressed bytes."""
+    torch = _torch()
+    from . import snappy, table
+    if stream is not None:  # (the masking between the steps is torch's: on the same stream)
+        with torch.cuda.stream(stream):
+            return read_blocks(image, handles, verify, max_bytes)
+    _require_cuda(image, handles)
+    _u8(image, "image")
+    _i64(handles, "handles")
+    if handles.numel() % 2:
+        raise ValueError("handles must be {offset, size} pairs")
+    n = handles.numel() // 2
+    dev = image.device
+    numel = image.numel()
+    if n == 0:
+        return (torch.zeros(0, dtype=torch.uint8, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
+                torch.zeros(0, dtype=torch.int32, device=dev))
+    h = handles.view(n, 2)
+    off, size = h[:, 0], h[:, 1]
+    zero = torch.zeros_like(off)
+    inside = (off >= 0) & (size >= 0) & (off <= numel) & (size <= numel - kBlockTrailerSize - off)
+    status = torch.where(inside, torch.full_like(off, READ_OK), torch.full_like(off, READ_TRUNCATED))
+    safe = torch.where(inside[:, None], h, torch.zeros_like(h)).reshape(-1).contiguous()
+    if verify and numel >= kBlockTrailerSize:
+        ok, _ = table.verify_blocks(image, safe)
+        status = torch.where(inside & (ok == 0), torch.full_like(status, READ_BAD_CHECKSUM), status)
+    if numel:
+        btype = torch.where(inside, image[torch.where(inside, off + size, zero)].to(torch.int64), zero)
+    else:
+        btype = zero
+    live = status == READ_OK
+    status = torch.where(live & (btype != kNoCompression) & (btype != kSnappyCompression),
+                         torch.full_like(status, READ_BAD_TYPE), status)
+    is_raw = live & (btype == kNoCompression)
+    is_comp = live & (btype == kSnappyCompression)
+    # the compressed blocks' places, from their preambles
+    ulen, pre_ok = _preamble(image, torch.where(is_comp, off, zero), torch.where(is_comp, size, zero)) \
+        if numel else (zero, is_comp)
+    status = torch.where(is_comp & ~pre_ok, torch.full_like(status, READ_BAD_COMPRESSED), status)
+    want = is_comp & pre_ok
+    too = want & (ulen > int(max_bytes))
+    asked = torch.where(want & ~too, ulen, zero)
+    too = too | (want & (torch.cumsum(asked, 0) > int(max_bytes)))
+    status = torch.where(too, torch.full_like(status, READ_TOO_LARGE), status)
+    want = want & ~too
+    # (a preamble the compressed bytes cannot meet gets no place: RawUncompress fails it)
+    placed = want & (ulen <= snappy.MAX_EXPANSION * size)
+    windows = torch.cat([torch.where(placed, ulen, zero), torch.where(is_raw, size, zero)]).contiguous()
+    _, places, end = pack_plan(windows, None, 0, 0)
+    csize = torch.where(want, size, zero)
+    coff = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(csize, 0, out=coff[1:])
+    total, ctotal = (int(x) for x in torch.stack([end[0], coff[-1]]).cpu())
+    contents = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)[:total]
+    places = places.view(2 * n, 2)
+    zeros8 = torch.zeros(n, dtype=torch.uint8, device=dev)
+    if ctotal:
+        # the compressed bytes side by side (snappy's blocks tile their buffer), then
+        # every block through RawUncompress: one that is not compressed has no input
+        # and no place, fails at its preamble and writes nothing
+        cbuf = torch.empty(ctotal, dtype=torch.uint8, device=dev)
+        pack(image, safe, None, None, zeros8, torch.stack([coff[:-1], csize], 1).reshape(-1).contiguous(), cbuf, 0)
+        _, len_ok = snappy.uncompressed_length(cbuf, coff)
+        out_offsets = torch.cat([places[:n, 0], places[n:n + 1, 0]]).contiguous()
+        room = contents if total else torch.empty(1, dtype=torch.uint8, device=dev)
+        _, _, ok, _ = snappy.uncompress(cbuf, coff, room, out_offsets)
+        status = torch.where(want & ((ok == 0) | (len_ok == 0)), torch.full_like(status, READ_BAD_COMPRESSED),
+                             status)
+    # the raw blocks
+    raw_dst = torch.stack([places[n:, 0], torch.where(is_raw, size, zero)], 1).reshape(-1).contiguous()
+    if total:
+        pack(image, safe, None, None, zeros8, raw_dst, contents, 0)
+    good = status == READ_OK
+    out_off = torch.where(is_raw, places[n:, 0], places[:n, 0])
+    out_size = torch.where(is_raw, size, ulen)
+    out_handles = torch.where(good[:, None], torch.stack([out_off, out_size], 1),
+                              torch.zeros_like(h)).reshape(-1).contiguous()
+    return contents, out_handles, status.to(torch.int32)
+
+
+# ---------------------------------------------------------------- the writer
+
+
+def _raise_on(status, what):
+    bad = [int(s) for s in status.cpu().tolist() if s != 0]
+    if bad:
+        raise ValueError(f"{what}: status {bad[0]}")
+
+
+def _offsets_of(sizes, dev):
+    """Host sizes -> (int64 n + 1 running sums on the device, their total)."""
+    torch = _torch()
+    offs = np.zeros(len(sizes) + 1, dtype=np.int64)
+    np.cumsum(np.asarray(sizes, dtype=np.int64), out=offs[1:])
+    return torch.from_numpy(offs).to(dev), int(offs[-1])
+
+
+def _compress(raw, offsets, sizes):
+    """snappy.compress of blocks that tile `raw` (host sizes): (comp, comp_offsets
+    int64[n], comp_len int64[n])."""
+    torch = _torch()
+    from . import snappy
+    caps = [32 + s + s // 6 for s in sizes]
+    out_offsets, total = _offsets_of(caps, raw.device)
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=raw.device)
+    _, _, clen = snappy.compress(raw, offsets, out, out_offsets)
+    return out, out_offsets[:-1].contiguous(), clen.contiguous()
+
+
+def _build_data_blocks(keys, key_offsets, values, value_image, block_first, sizes, restart_interval, compression):
+    """The data blocks built side by side into a staging image and, under
+    kSnappyCompression, compressed: _Blocks."""
+    torch = _torch()
+    from . import block_build
+    dev = keys.device
+    offsets, total = _offsets_of(sizes, dev)
+    raw = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)[:total]
+    raw_handles = torch.stack([offsets[:-1], offsets[1:] - offsets[:-1]], 1).reshape(-1).contiguous()
+    if len(sizes):
+        _, st = block_build.build(keys, key_offsets, values, value_image, block_first, raw, raw_handles,
+                                  restart_interval)
+        _raise_on(st, "build")
+    if compression == kSnappyCompression and len(sizes):
+        comp, comp_offsets, comp_len = _compress(raw, offsets, sizes)
+        return _Blocks(raw, raw_handles, comp, comp_offsets, comp_len)
+    return _Blocks(raw, raw_handles, None, None, None)
+
+
+def _finish_table(keys, key_offsets, block_first, blocks, cmp, restart_interval, bits_per_key, compression):
+    """TableBuilder from the first WriteBlock to the footer, over data blocks
+    that are already built (and compressed): block b = entries
+    [block_first[b], block_first[b+1]) of keys / key_offsets.  Returns
+    (image, data_handles, index_handle)."""
+    torch = _torch()
+    from . import block_build, bloom
+    dev = keys.device
+    n = key_offsets.numel() - 1
+    nb = block_first.numel() - 1
+    snappy_on = compression == kSnappyCompression
+    # 1. WriteBlock's rule over the data blocks; 2. the one read of their handles
+    raw_len = blocks.raw_handles.view(-1, 2)[:, 1].contiguous() if nb else \
+        torch.zeros(0, dtype=torch.int64, device=dev)
+    d_types, d_handles, d_end = pack_plan(raw_len, blocks.comp_len if snappy_on else None)
+    host = torch.cat([d_handles, d_end, block_first]).cpu().numpy()
+    data_handles, data_end, first_host = host[:2 * nb], int(host[2 * nb]), host[2 * nb + 1:]
+    # 3. the filter block: StartBlock sees the packed offsets
+    filt = None
+    if bits_per_key is not None:
+        starts = list(data_handles[0::2]) + ([data_end] if nb else [])
+        firsts = list(first_host) + ([n] if nb else [])
+        filt = bloom.build_filter_block(keys, key_offsets, starts, firsts, int(bits_per_key),
+                                        strip=8 if cmp == INTERNAL_KEY else 0)
+    # 4. the metaindex block and 5. the index block, raw, side by side in a staging image
+    if filt is not None:
+        meta_value = block_build.encode_handle(data_end, len(filt))
+        m_keys = torch.tensor(list(block_build.FILTER_KEY), dtype=torch.uint8, device=dev)
+        m_off = torch.tensor([0, len(block_build.FILTER_KEY)], dtype=torch.int64, device=dev)
+        m_values = torch.tensor([0, len(meta_value)], dtype=torch.int64, device=dev)
+        m_image = torch.tensor(list(meta_value), dtype=torch.uint8, device=dev)
+        m_first = torch.tensor([0, 1], dtype=torch.int64, device=dev)
+        meta_size = 3 + len(block_build.FILTER_KEY) + len(meta_value) + 8
+    else:
+        m_keys = torch.zeros(0, dtype=torch.uint8, device=dev)
+        m_off = torch.zeros(1, dtype=torch.int64, device=dev)
+        m_values = torch.zeros(0, dtype=torch.int64, device=dev)
+        m_image = torch.zeros(0, dtype=torch.uint8, device=dev)
+        m_first = torch.zeros(2, dtype=torch.int64, device=dev)
+        meta_size = 8
+    tbf = torch.tensor([0, nb], dtype=torch.int64, device=dev)
+    isize, ist = block_build.index_block(keys, key_offsets, block_first, tbf, d_handles, cmp)
+    _raise_on(ist, "index block")
+    index_size = int(isize[0])
+    filt_size = len(filt) if filt is not None else 0
+    tail_sizes = ([filt_size] if filt is not None else []) + [meta_size, index_size]
+    tail_offsets, tail_total = _offsets_of(tail_sizes, dev)
+    tail = torch.zeros(tail_total, dtype=torch.uint8, device=dev)
+    tail_raw_handles = torch.stack([tail_offsets[:-1], tail_offsets[1:] - tail_offsets[:-1]], 1).reshape(-1).contiguous()
+    if filt is not None:
+        tail[:filt_size] = torch.from_numpy(np.frombuffer(filt, dtype=np.uint8).copy()).to(dev)
+    _, st = block_build.build(m_keys, m_off, m_values, m_image, m_first, tail,
+                              tail_raw_handles[-4:-2].contiguous(), restart_interval)
+    _raise_on(st, "metaindex block")
+    _, st = block_build.index_block(keys, key_offsets, block_first, tbf, d_handles, cmp, tail,
+                                    tail_raw_handles[-2:].contiguous())
+    _raise_on(st, "index block")
+    tail_comp = tail_comp_offsets = tail_comp_len = None
+    if snappy_on:
+        tail_comp, tail_comp_offsets, tail_comp_len = _compress(tail, tail_offsets, tail_sizes)
+        if filt is not None:  # the filter block is WriteRawBlock(kNoCompression)
+            tail_comp_len = tail_comp_len.clone()
+            tail_comp_len[0] = COMP_NONE
+    tail_raw_len = torch.tensor(tail_sizes, dtype=torch.int64, device=dev)
+    t_types, t_handles, t_end = pack_plan(tail_raw_len, tail_comp_len, data_end)
+    t_host = torch.cat([t_handles, t_end]).cpu().numpy()
+    end = int(t_host[-1])
+    meta_handle = (int(t_host[-5]), int(t_host[-4]))
+    index_handle = (int(t_host[-3]), int(t_host[-2]))
+    # 6. everything to its place, every trailer, the footer
+    image = torch.zeros(end + block_build.kFooterEncodedLength, dtype=torch.uint8, device=dev)
+    if nb:
+        _raise_on(pack(blocks.raw, blocks.raw_handles, blocks.comp if snappy_on else None,
+                       blocks.comp_offsets if snappy_on else None, d_types, d_handles, image), "pack")
+    _raise_on(pack(tail, tail_raw_handles, tail_comp, tail_comp_offsets, t_types, t_handles, image), "pack")
+    seal_blocks(image, torch.cat([d_handles, t_handles]).contiguous(), torch.cat([d_types, t_types]).contiguous())
+    image[end:] = torch.tensor(list(block_build.footer(meta_handle, index_handle)), dtype=torch.uint8, device=dev)
+    return image, d_handles, index_handle
+
+
+def write_table(keys, key_offsets, values, value_image, cmp=INTERNAL_KEY, block_size=4096, restart_interval=16,
+                bits_per_key=None, compression=kSnappyCompression, stream=None):
+    """TableBuilder (table/table_builder.cc) Add for every entry, then Finish,
+    with WriteBlock's rule (the snappy form is kept where it is smaller than
+    raw - raw / 8) on the data blocks, the metaindex block and the index block;
+    the filter block is written raw.  The flush rule looks at the uncompressed
+    estimate, so the plan is block_build.plan's.  The data blocks are built
+    into a staging image, compressed and laid out by pack_plan; their packed
+    offsets feed the filter block and the index block; then every block is
+    moved to its place, sealed with its type, and the footer follows.  With
+    compression=kNoCompression the bytes are block_build.table_build's.
+    Returns (file_image uint8 device tensor, data_handles int64 device tensor
+    of {offset, size} pairs, index_handle (offset, size))."""
+    torch = _torch()
+    from . import block_build
+    if compression not in (kNoCompression, kSnappyCompression):
+        raise ValueError("unknown compression type")
+    if cmp not in (BYTEWISE, INTERNAL_KEY):
+        raise ValueError("unknown comparator")
+    if stream is not None:  # (the copies between the steps are torch's: on the same stream)
+        with torch.cuda.stream(stream):
+            return write_table(keys, key_offsets, values, value_image, cmp, block_size, restart_interval,
+                               bits_per_key, compression)
+    _require_cuda(keys, key_offsets, values, value_image)
+    dev = keys.device
+    n = key_offsets.numel() - 1
+    if n < 0 or values.numel() != 2 * n:
+        raise ValueError("values must be one {offset, length} pair per entry")
+    values = values.reshape(-1)
+    p = block_build.plan(keys, key_offsets, values, torch.tensor([0, n], dtype=torch.int64, device=dev),
+                         block_size, restart_interval)
+    _raise_on(p.status, "plan")
+    nb = int(p.table_block_first[-1])
+    sizes = p.block_bytes[:nb].cpu().tolist()
+    block_first = p.block_first[:nb + 1].contiguous()
+    blocks = _build_data_blocks(keys, key_offsets, values, value_image, block_first, sizes, restart_interval,
+                                compression)
+    return _finish_table(keys, key_offsets, block_first, blocks, cmp, restart_interval, bits_per_key, compression)
+
+
+# ---------------------------------------------------------------- Get
+
+
+def _get_state_of(read_status):
+    """read_blocks' status -> table_get's state (int64 tensors)."""
+    torch = _torch()
+    out = torch.full_like(read_status, SEEK_VALID)
+    for r, g in ((READ_TRUNCATED, SEEK_BAD_HANDLE), (READ_BAD_CHECKSUM, GET_BAD_CHECKSUM),
+                 (READ_BAD_COMPRESSED, GET_BAD_COMPRESSED), (READ_BAD_TYPE, GET_BAD_TYPE),
+                 (READ_TOO_LARGE, GET_BAD_COMPRESSED)):
+        out = torch.where(read_status == r, torch.full_like(out, g), out)
+    return out
+
+
+def table_get(image, index_handle, keys, key_offsets, filter=None, verify=True,  # noqa: A002
+              cmp=INTERNAL_KEY, bits_per_key=10, bloom_bits_use=15, max_bytes=1 << 30, stream=None):
+    """Table::InternalGet (table/table.cc:309-339) for a batch of keys over a
+    device-resident table image whose blocks are of either type.  The index
+    block goes through read_blocks, the queries are seeked in it, the distinct
+    data blocks they hit go through read_blocks once each (one host read of
+    their count, one of the contents' size), and the data-block Seek runs over
+    the contents.
+
+    Returns GetResult(state, key_len, value, data_handle, value_image) as
+    block.table_get does, with two differences: value {offset, length} points
+    into value_image (the uncompressed contents, not the file image), and a
+    block that does not uncompress is GET_BAD_COMPRESSED; GET_NEEDS_UNCOMPRESS
+    never appears.  An index block that cannot be read gives every query its
+    state."""
+    torch = _torch()
+    from . import block, bloom
+    if stream is not None:  # (the masking between the steps is torch's: on the same stream)
+        with torch.cuda.stream(stream):
+            return table_get(image, index_handle, keys, key_offsets, filter, verify, cmp, bits_per_key,
+                             bloom_bits_use, max_bytes)
+    _require_cuda(image, keys, key_offsets, filter)
+    _u8(image, "image")
+    _u8(keys, "keys")
+    _i64(key_offsets, "key_offsets")
+    n = key_offsets.numel() - 1
+    dev = image.device
+    ih = torch.tensor([int(index_handle[0]), int(index_handle[1])], dtype=torch.int64, device=dev)
+    # 1. the index block's contents; iiter->Seek(k) and BlockHandle::DecodeFrom(iiter->value())
+    icontents, ihandle, istatus = read_blocks(image, ih, verify, max_bytes)
+    if icontents.numel() == 0:
+        icontents = torch.zeros(1, dtype=torch.uint8, device=dev)
+    idx = block.seek(icontents, ihandle.repeat(n), keys, key_offsets, cmp=cmp, value_is_handle=True)
+    index_state = _get_state_of(istatus.to(torch.int64))[0].to(torch.int32)
+    state = torch.where(index_state != SEEK_VALID, index_state.expand(n), idx.state).contiguous()
+    found = state == SEEK_VALID
+    handle = torch.where(found[:, None], idx.handle, torch.zeros_like(idx.handle))
+    if filter is not None:  # 2. filter->KeyMayMatch(handle.offset(), k)
+        _u8(filter, "filter")
+        fh = torch.tensor([0, filter.numel()], dtype=torch.int64, device=dev).repeat(n)
+        may, _ = bloom.filter_block_may_match(filter, fh, handle[:, 0].contiguous(), keys, key_offsets,
+                                              bits_per_key, bloom_bits_use,
+                                              strip=8 if cmp == INTERNAL_KEY else 0)
+        state = torch.where(found & (may == 0), torch.full_like(state, GET_FILTERED), state)
+    live = state == SEEK_VALID
+    # 3. ReadBlock of the distinct data blocks (a query that ended above asks for no block)
+    asked = torch.where(live[:, None], handle, torch.full_like(handle, -1))
+    blocks, which = torch.unique(asked, dim=0, return_inverse=True)
+    contents, out_handles, bstatus = read_blocks(image, blocks.reshape(-1).contiguous(), verify, max_bytes)
+    if contents.numel() == 0:
+        contents = torch.zeros(1, dtype=torch.uint8, device=dev)[:0]
+    bstate = _get_state_of(bstatus.to(torch.int64))[which].to(torch.int32)
+    state = torch.where(live, bstate, state)
+    live = state == SEEK_VALID
+    # 4. block_iter->Seek(k) over the contents
+    dh = torch.where(live[:, None], out_handles.view(-1, 2)[which], torch.zeros_like(handle))
+    seek_image = contents if contents.numel() else torch.zeros(1, dtype=torch.uint8, device=dev)
+    dat = block.seek(seek_image, dh.reshape(-1).contiguous(), keys, key_offsets, cmp=cmp)
+    state = torch.where(live, dat.state, state)
+    hit = state == SEEK_VALID
+    key_len = torch.where(hit, dat.key_len, torch.zeros_like(dat.key_len))
+    value = torch.where(hit[:, None], dat.value, torch.zeros_like(dat.value))
+    return GetResult(state, key_len, value, handle, contents)
+
+
+# ---------------------------------------------------------------- compaction
+
+
+def index_data_handles(image, index_handle, verify=True):
+    """The data block handles an index block of either type lists, as an int64
+    numpy array of {offset, size} pairs."""
+    torch = _torch()
+    from . import block
+    from .merge import _get_varint64
+    ih = torch.tensor([int(index_handle[0]), int(index_handle[1])], dtype=torch.int64, device=image.device)
+    contents, oh, st = read_blocks(image, ih, verify)
+    if int(st.cpu()[0]) != READ_OK:
+        raise ValueError("index block: " + READ_MESSAGE[int(st.cpu()[0])])
+    _, _, values, _, dst = block.decode(contents, oh)
+    if int(dst.cpu()[0]) != block.BLOCK_OK:
+        raise ValueError("index block: " + block.STATUS_MESSAGE.get(int(dst.cpu()[0]), "bad"))
+    buf = contents.cpu().numpy().tobytes()
+    out = []
+    for off, _ in values.cpu().tolist():
+        o, p = _get_varint64(buf, off)
+        s, _ = _get_varint64(buf, p)
+        out += [o, s]
+    return np.array(out, dtype=np.int64)
+
+
+def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None, cmp=INTERNAL_KEY, drop=False,
+            smallest_snapshot=None, bottom_level=False, block_size=4096, restart_interval=16, bits_per_key=None,
+            compression=kNoCompression, verify=True, stream=None):
+    """merge.compact for tables whose blocks are of either type, with output
+    tables written under `compression`.  Every input data block goes through
+    read_blocks, whose contents are the value image that decode, merge and the
+    builder point into.  The merged entries are planned as one table; every
+    data block of that plan is built and compressed once; the cut
+    (merge.cut_tables) sees each block's packed size, as FileSize() does; and
+    each output table is finished from its slice of those blocks.  Returns
+    [OutputTable(image, data_handles, index_handle)]."""
+    torch = _torch()
+    from . import block, block_build, merge
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return compact(images, data_handles, max_file_size, index_handles, cmp, drop, smallest_snapshot,
+                           bottom_level, block_size, restart_interval, bits_per_key, compression, verify)
+    if (data_handles is None) == (index_handles is None):
+        raise ValueError("give data_handles or index_handles")
+    if compression not in (kNoCompression, kSnappyCompression):
+        raise ValueError("unknown compression type")
+    if len(images) > merge.MAX_RUNS:
+        raise ValueError(f"at most {merge.MAX_RUNS} input tables")
+    if int(max_file_size) < 1:
+        raise ValueError("max_file_size must be at least 1")
+    _require_cuda(*images)
+    if not images:
+        return []
+    dev = images[0].device
+    if data_handles is None:
+        data_handles = [index_data_handles(img, ih, verify) for img, ih in zip(images, index_handles)]
+    if len(data_handles) != len(images):
+        raise ValueError("one set of handles per image")
+    # 1. one file image; every handle moves by its image's place in it
+    image = torch.cat([img.reshape(-1) for img in images])
+    handles, blocks_before, base = [], [0], 0
+    for img, h in zip(images, data_handles):
+        h = torch.as_tensor(np.asarray(h.cpu() if hasattr(h, "cpu") else h, dtype=np.int64).reshape(-1, 2).copy())
+        h[:, 0] += base
+        handles.append(h)
+        blocks_before.append(blocks_before[-1] + h.shape[0])
+        base += img.numel()
+    handles = torch.cat(handles).reshape(-1).contiguous().to(dev)
+    # 2. ReadBlock of every data block; the entries, one run per input table
+    contents, handles, st = read_blocks(image, handles, verify)
+    bad = [(b, int(s)) for b, s in enumerate(st.cpu().tolist()) if s != READ_OK]
+    if bad:
+        raise ValueError(f"input data block {bad[0][0]}: {READ_MESSAGE[bad[0][1]]}")
+    if contents.numel() == 0:
+        return []
+    counts, st = block.scan(contents, handles)
+    _raise_on(st, "scan")
+    nb = counts.shape[0]
+    entry_base = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+    key_base = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+    if nb:
+        torch.cumsum(counts[:, 0], 0, out=entry_base[1:])
+        torch.cumsum(counts[:, 1], 0, out=key_base[1:])
+    keys, key_offsets, values, _, st = block.decode(contents, handles, entry_base, key_base)
+    _raise_on(st, "decode")
+    run_first = entry_base[torch.tensor(blocks_before, dtype=torch.int64, device=dev)].contiguous()
+    # 3. the merge and the single-table plan of its output
+    m = merge.merge(keys, key_offsets, values, run_first, cmp, drop, smallest_snapshot, bottom_level)
+    bad = [(r, int(s)) for r, s in enumerate(m.run_status.cpu().tolist()) if s != merge.MERGE_OK]
+    if bad:
+        raise ValueError(f"input table {bad[0][0]}: {merge.STATUS_MESSAGE.get(bad[0][1], bad[0][1])}")
+    n_out = m.key_offsets.numel() - 1
+    if n_out == 0:
+        return []
+    m_values = m.values.reshape(-1).contiguous()
+    p = block_build.plan(m.keys, m.key_offsets, m_values, torch.tensor([0, n_out], dtype=torch.int64, device=dev),
+                         block_size, restart_interval)
+    _raise_on(p.status, "plan")
+    n_blocks = int(p.table_block_first[-1])
+    block_first = p.block_first[:n_blocks + 1].contiguous()
+    first_host = block_first.cpu().tolist()
+    sizes = p.block_bytes[:n_blocks].cpu().tolist()
+    # 4. every data block once: built, compressed, ruled; the cut over the packed sizes
+    blocks = _build_data_blocks(m.keys, m.key_offsets, m_values, contents, block_first, sizes, restart_interval,
+                                compression)
+    _, packed, _ = pack_plan(blocks.raw_handles.view(-1, 2)[:, 1].contiguous(), blocks.comp_len)
+    table_first, table_block_first = merge.cut_tables(first_host, packed.view(-1, 2)[:, 1].cpu().tolist(),
+                                                      int(max_file_size))
+    # 5. each output table from its slice of the entries and of the blocks
+    out = []
+    key_at = m.key_offsets[torch.tensor(table_first, dtype=torch.int64, device=dev)].cpu().tolist()
+    for t in range(len(table_first) - 1):
+        e0, e1 = table_first[t], table_first[t + 1]
+        b0, b1 = table_block_first[t], table_block_first[t + 1]
+        t_off = (m.key_offsets[e0:e1 + 1] - key_at[t]).contiguous()
+        t_keys = m.keys[key_at[t]:key_at[t + 1]].contiguous()
+        t_blocks = _Blocks(blocks.raw, blocks.raw_handles[2 * b0:2 * b1].contiguous(), blocks.comp,
+                           blocks.comp_offsets[b0:b1].contiguous() if blocks.comp is not None else None,
+                           blocks.comp_len[b0:b1].contiguous() if blocks.comp is not None else None)
+        out.append(OutputTable(*_finish_table(t_keys, t_off, (block_first[b0:b1 + 1] - e0).contiguous(), t_blocks,
+                                              cmp, restart_interval, bits_per_key, compression)))
+    return out
