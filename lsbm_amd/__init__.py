@@ -13,12 +13,15 @@
                     drop rule and output-file cut, input table images -> output table files
   lsbm_amd.sstable  tables with snappy-compressed blocks: WriteBlock's keep rule and block packing,
                     batched ReadBlock, table writer, Get and compaction over either block type
+  lsbm_amd.memtable memtable flush: batched WriteBatch::Iterate over log records, the memtable's
+                    iteration order as a sort, log image -> Level-0 table file
 
 The compute lives in lsbm_amd/liblsbm_crc32c.so (hand-written gfx950 HIP
 kernels behind the C ABIs in include/lsbm_crc32c.h, include/lsbm_bloom.h, include/lsbm_snappy.h and
-include/lsbm_block.h, include/lsbm_block_build.h, include/lsbm_merge.h, include/lsbm_table_pack.h).
+include/lsbm_block.h, include/lsbm_block_build.h, include/lsbm_merge.h, include/lsbm_table_pack.h,
+include/lsbm_memtable.h).
 """
 from ._lib import LIB_PATH, LsbmError, lib  # noqa: F401
 
 __all__ = ["LIB_PATH", "LsbmError", "lib", "crc32c", "engine", "table", "log", "bloom", "snappy",
-           "block", "block_build", "merge", "sstable"]
+           "block", "block_build", "merge", "sstable", "memtable"]

@@ -130,6 +130,14 @@ TABLE_PACK_SIGNATURES = {
                                    _vp]),
 }
 
+# every symbol include/lsbm_memtable.h declares
+MEMTABLE_SIGNATURES = {
+    "lsbm_wb_scan_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "lsbm_wb_decode_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "lsbm_memtable_sort_scratch_bytes": (_u64, [_u64]),
+    "lsbm_memtable_sort_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+}
+
 _lib = None
 
 
@@ -151,7 +159,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(BLOCK_SIGNATURES.items())
                                   + list(BLOCK_BUILD_SIGNATURES.items()) + list(MERGE_SIGNATURES.items())
-                                  + list(TABLE_PACK_SIGNATURES.items())):
+                                  + list(TABLE_PACK_SIGNATURES.items()) + list(MEMTABLE_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)

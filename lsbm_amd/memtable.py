@@ -1,0 +1,319 @@
+"""Memtable flush (WriteBatchInternal::InsertInto, MemTable::Add, the skiplist's
+order and BuildTable of lsbm: DBImpl::RecoverLogFile / WriteLevel0Table,
+lsbm/db_impl.cc:433-540) on the GPU.
+
+Thin wrappers over include/lsbm_memtable.h and the other modules.  Device
+tensors in, device tensors out; every call enqueues on `stream` (default:
+torch's current stream).
+
+    scan(image, records)               WriteBatch::Iterate of every record:
+                                       entries, user-key bytes, status
+    decode(image, records, ...)        the same walk written out: internal keys
+                                       + key_offsets and value {offset, length}
+                                       slices, and the largest sequence number
+    sort(keys, key_offsets)            the memtable's iteration order as a
+                                       merge.PlanResult (merge.gather gathers it)
+    entries(image, records, ...)       scan + decode + sort + gather: what
+                                       MemTable::NewIterator() returns
+    flush(image, records, ...)         entries, then sstable.write_table: the
+                                       Level-0 table file (BuildTable)
+    log_records(image_host)            a log file's logical records as
+                                       {offset, length} pairs, fragments
+                                       assembled on the device
+    recover_log(image_host, ...)       log_records, then flush
+
+A record is image[records[2i], records[2i] + records[2i+1]): one
+WriteBatch::rep_ (int64 {offset, length} pairs).  Entries are what block.decode
+returns and block_build, bloom, merge and sstable.write_table read.  One call
+is one memtable: the caller chooses which records go in.
+"""
+from collections import namedtuple
+
+import numpy as np
+
+from ._lib import check, lib
+from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .log import kBlockSize, kFirstType, kFullType, kHeaderSize, kLastType, kMiddleType
+from .merge import MERGE_OK, PlanResult
+from .table import kNoCompression
+
+# per-record status (include/lsbm_memtable.h)
+WB_OK = 0
+WB_TOO_SMALL = 1
+WB_BAD_PUT = 2
+WB_BAD_DELETE = 3
+WB_UNKNOWN_TAG = 4
+WB_WRONG_COUNT = 5
+WB_BAD_INPUT = 6
+WB_NO_ROOM = 7
+
+# the reference's words for each (common/write_batch.cc:42-80, lsbm/db_impl.cc:440-443)
+STATUS_MESSAGE = {WB_TOO_SMALL: "log record too small", WB_BAD_PUT: "bad WriteBatch Put",
+                  WB_BAD_DELETE: "bad WriteBatch Delete", WB_UNKNOWN_TAG: "unknown WriteBatch tag",
+                  WB_WRONG_COUNT: "WriteBatch has wrong count", WB_BAD_INPUT: "record reaches outside the image",
+                  WB_NO_ROOM: "record window too small"}
+
+DecodeResult = namedtuple("DecodeResult", "keys key_offsets values max_sequence status")
+EntriesResult = namedtuple("EntriesResult", "keys key_offsets values status max_sequence")
+FlushResult = namedtuple("FlushResult", "image data_handles index_handle smallest largest max_sequence status")
+
+
+def _check(**ts):
+    """dtype / layout checks for the tensors a kernel will read or write."""
+    torch = _torch()
+    for name, t in ts.items():
+        if t is None:
+            continue
+        w = torch.uint8 if name in ("image", "keys") else torch.int64
+        if t.dtype != w:
+            raise ValueError(f"{name} must be {w}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+
+
+def _n_records(records):
+    if records.numel() % 2:
+        raise ValueError("records must be {offset, length} pairs")
+    return records.numel() // 2
+
+
+def scan(image, records, stream=None):
+    """(counts int64[n, 2] = {entries, user-key bytes}, status int32[n])."""
+    torch = _torch()
+    _require_cuda(image, records)
+    _check(image=image, records=records)
+    n = _n_records(records)
+    counts = torch.zeros((n, 2), dtype=torch.int64, device=image.device)
+    status = torch.zeros(n, dtype=torch.int32, device=image.device)
+    check(lib().lsbm_wb_scan_dev(_ptr(image), image.numel(), _ptr(records), n, _ptr(counts), _ptr(status),
+                                 _stream_ptr(stream)), "lsbm_wb_scan_dev")
+    return counts, status
+
+
+def bases(counts):
+    """The running sums decode takes, from a scan's counts: (entry_base,
+    key_base), n + 1 each; an entry's internal key is its user key and 8 bytes."""
+    torch = _torch()
+    n = counts.shape[0]
+    entry_base = torch.zeros(n + 1, dtype=torch.int64, device=counts.device)
+    key_base = torch.zeros(n + 1, dtype=torch.int64, device=counts.device)
+    if n:
+        torch.cumsum(counts[:, 0], 0, out=entry_base[1:])
+        torch.cumsum(counts[:, 1] + 8 * counts[:, 0], 0, out=key_base[1:])
+    return entry_base, key_base
+
+
+def decode(image, records, entry_base=None, key_base=None, keys=None, key_offsets=None, values=None, stream=None):
+    """DecodeResult(keys, key_offsets, values int64[entries, 2], max_sequence
+    int64[1] (the 64 bits of the unsigned number), status int32[n]).  Record
+    i's entries are [entry_base[i], entry_base[i+1]).  Without entry_base /
+    key_base they are the running sums of a scan's counts; without the outputs
+    one device -> host read of the totals sizes them."""
+    torch = _torch()
+    _require_cuda(image, records, entry_base, key_base, keys, key_offsets, values)
+    _check(image=image, records=records, entry_base=entry_base, key_base=key_base, keys=keys,
+           key_offsets=key_offsets, values=values)
+    n = _n_records(records)
+    dev = image.device
+    if (entry_base is None) != (key_base is None):
+        raise ValueError("entry_base and key_base come together")
+    if entry_base is None:
+        entry_base, key_base = bases(scan(image, records, stream)[0])
+    if entry_base.numel() != n + 1 or key_base.numel() != n + 1:
+        raise ValueError("entry_base and key_base need n + 1 entries")
+    if key_offsets is None or values is None or keys is None:
+        totals = torch.stack([entry_base[-1], key_base[-1]]).cpu()
+        ne, nk = int(totals[0]), int(totals[1])
+        if key_offsets is None:
+            key_offsets = torch.zeros(ne + 1, dtype=torch.int64, device=dev)
+        if values is None:
+            values = torch.zeros((max(ne, 1), 2), dtype=torch.int64, device=dev)[:ne]
+        if keys is None:
+            keys = torch.zeros(max(nk, 1), dtype=torch.uint8, device=dev)[:nk]
+    entries_cap = min(key_offsets.numel() - 1, values.numel() // 2)
+    if entries_cap < 0:
+        raise ValueError("key_offsets needs at least one entry")
+    max_sequence = torch.zeros(1, dtype=torch.int64, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    check(lib().lsbm_wb_decode_dev(_ptr(image), image.numel(), _ptr(records), n, _ptr(entry_base), _ptr(key_base),
+                                   _ptr(keys), keys.numel(), _ptr(key_offsets), _ptr(values), entries_cap,
+                                   _ptr(max_sequence), _ptr(status), _stream_ptr(stream)), "lsbm_wb_decode_dev")
+    return DecodeResult(keys, key_offsets, values, max_sequence, status)
+
+
+def sort(keys, key_offsets, stream=None):
+    """merge.PlanResult(source int64[n], out_key_offsets int64[n + 1], counts
+    int64[2] = {n, key bytes}, run_status int32[1]): the memtable's iteration
+    order of the internal keys -- user key ascending, tag descending, among
+    equal internal keys the later entry first.  merge.gather gathers it."""
+    torch = _torch()
+    _require_cuda(keys, key_offsets)
+    _check(keys=keys, key_offsets=key_offsets)
+    n = key_offsets.numel() - 1
+    if n < 0:
+        raise ValueError("key_offsets needs at least one entry")
+    dev = keys.device
+    source = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)[:n]
+    out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    scratch_bytes = lib().lsbm_memtable_sort_scratch_bytes(n)
+    scratch = torch.empty((scratch_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    check(lib().lsbm_memtable_sort_dev(_ptr(keys), keys.numel(), _ptr(key_offsets), n, _ptr(source), _ptr(out_off),
+                                       _ptr(counts), _ptr(status), _ptr(scratch), scratch.numel() * 8,
+                                       _stream_ptr(stream)), "lsbm_memtable_sort_dev")
+    return PlanResult(source, out_off, counts, status)
+
+
+def max_sequence_of(t):
+    """The unsigned 64-bit number in decode's max_sequence tensor."""
+    return int(t.cpu()[0]) & ((1 << 64) - 1)
+
+
+def entries(image, records, paranoid=False, stream=None):
+    """What the reference's memtable holds after InsertInto of every record, in
+    NewIterator()'s order: EntriesResult(keys, key_offsets, values int64[n, 2],
+    status int32[records], max_sequence int).  scan, decode, sort and
+    merge.gather run on one stream; the host reads the two totals that size the
+    entries after the scan, and the statuses after the gather.  A record in
+    error contributes the entries before its error (paranoid_checks false);
+    with paranoid=True the first such record raises ValueError with the
+    reference's message."""
+    torch = _torch()
+    from . import merge
+    if stream is not None:  # (the sums between the steps are torch's: on the same stream)
+        with torch.cuda.stream(stream):
+            return entries(image, records, paranoid)
+    counts, _ = scan(image, records)
+    entry_base, key_base = bases(counts)
+    d = decode(image, records, entry_base, key_base)
+    p = sort(d.keys, d.key_offsets)
+    flat = d.values.reshape(-1)
+    g = merge.gather(d.keys, d.key_offsets, flat, p)
+    # the one read after the chain: how many records are in error, sort's and gather's status
+    n_bad, sort_st, gather_st = torch.stack([(d.status != WB_OK).sum().to(torch.int32), p.run_status[0],
+                                             g.status[0]]).cpu().tolist()
+    if n_bad:  # (only then the statuses themselves)
+        status = d.status.cpu().tolist()
+        for r, st in enumerate(status):
+            if st in (WB_BAD_INPUT, WB_NO_ROOM) or (paranoid and st != WB_OK):
+                raise ValueError(f"record {r}: {STATUS_MESSAGE.get(st, st)}")
+    if sort_st != MERGE_OK or gather_st != MERGE_OK:
+        raise ValueError(f"internal error: sort status {sort_st}, gather status {gather_st}")
+    return EntriesResult(g.keys, g.key_offsets, g.values, d.status, max_sequence_of(d.max_sequence))
+
+
+def flush(image, records, compression=kNoCompression, block_size=4096, restart_interval=16, bits_per_key=None,
+          paranoid=False, stream=None):
+    """BuildTable (lsbm/builder.cc:36-48) over the memtable of `records`:
+    FlushResult(image, data_handles, index_handle, smallest, largest,
+    max_sequence, status).  image is the Level-0 table file (a uint8 device
+    tensor) with the internal-key comparator and, with bits_per_key, the
+    InternalFilterPolicy bloom; smallest / largest are the first and the last
+    internal key as bytes (FileMetaData).  Without an entry no table is written:
+    image, data_handles, index_handle, smallest and largest are None."""
+    torch = _torch()
+    from . import sstable
+    from .block import INTERNAL_KEY
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return flush(image, records, compression, block_size, restart_interval, bits_per_key, paranoid)
+    e = entries(image, records, paranoid)
+    n = e.key_offsets.numel() - 1
+    if n == 0:
+        return FlushResult(None, None, None, None, None, e.max_sequence, e.status)
+    values = e.values.reshape(-1).contiguous()
+    table, data_handles, index_handle = sstable.write_table(e.keys, e.key_offsets, values, image, INTERNAL_KEY,
+                                                            block_size, restart_interval, bits_per_key, compression)
+    ends = e.key_offsets[torch.tensor([1, n - 1], device=e.key_offsets.device)].cpu().tolist()
+    smallest = bytes(e.keys[:ends[0]].cpu().numpy())
+    largest = bytes(e.keys[ends[1]:].cpu().numpy())
+    return FlushResult(table, data_handles, index_handle, smallest, largest, e.max_sequence, e.status)
+
+
+def _framing(buf):
+    """The physical records of a cleanly framed log image: [(header offset,
+    payload length, type)].  Anything log::Reader would report raises."""
+    def fault(what, at):
+        raise ValueError(f"{what} at offset {at}: not a cleanly framed log; lsbm::log::BatchReader "
+                         "(include/lsbm/log_checksum.h) reads such a log with the reference's reporter semantics")
+    out, pos, n = [], 0, len(buf)
+    while pos < n:
+        left = kBlockSize - pos % kBlockSize
+        if left < kHeaderSize:  # the block's trailer
+            pos += left
+            continue
+        if n - pos < kHeaderSize:
+            fault("truncated record header", pos)
+        length, t = int(buf[pos + 4]) | int(buf[pos + 5]) << 8, int(buf[pos + 6])
+        if kHeaderSize + length > left or pos + kHeaderSize + length > n:
+            fault("bad record length", pos)
+        if t not in (kFullType, kFirstType, kMiddleType, kLastType):
+            fault(f"unknown record type {t}", pos)
+        out.append((pos, length, t))
+        pos += kHeaderSize + length
+    return out
+
+
+def log_records(image_host, device="cuda", stream=None):
+    """(image, records): the logical records of a log file (bytes or a uint8
+    numpy array) as log::Reader::ReadRecord returns them, for scan / entries /
+    flush.  Every physical record's CRC is verified on the device
+    (log.verify_records).  An unfragmented record is its payload in place; the
+    fragments of a FIRST / MIDDLE / LAST record are put together by
+    lsbm_gather_dev in a side image that follows the log's bytes in `image`.
+    A framing or CRC fault raises ValueError."""
+    torch = _torch()
+    from . import log
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return log_records(image_host, device)
+    buf = np.frombuffer(bytes(image_host), dtype=np.uint8) if isinstance(image_host, (bytes, bytearray)) \
+        else np.ascontiguousarray(image_host, dtype=np.uint8)
+    physical = _framing(buf)
+    # the logical records: (offset, length) in place, or a list of fragments
+    records, parts, side = [], None, []
+    for pos, length, t in physical:
+        if (t in (kFullType, kFirstType)) != (parts is None):
+            raise ValueError(f"fragment out of order at offset {pos}: lsbm::log::BatchReader reads such a log")
+        if t == kFullType:
+            records.append((pos + kHeaderSize, length))
+            continue
+        if t == kFirstType:
+            parts = []
+        parts.append((pos + kHeaderSize, length))
+        if t == kLastType:
+            total = sum(ln for _, ln in parts)
+            records.append((len(buf) + sum(ln for _, _, ln in side), total))
+            at = records[-1][0]
+            for off, ln in parts:
+                side.append((off, at, ln))
+                at += ln
+            parts = None
+    if parts is not None:
+        raise ValueError("the log ends inside a fragmented record: lsbm::log::BatchReader reads such a log")
+    side_bytes = sum(ln for _, _, ln in side)
+    image = torch.zeros(max(len(buf) + side_bytes, 1), dtype=torch.uint8, device=device)[:len(buf) + side_bytes]
+    if len(buf):
+        image[:len(buf)] = torch.from_numpy(buf.copy()).to(device)
+    if physical:
+        heads = torch.tensor([p for p, _, _ in physical], dtype=torch.int64, device=device)
+        _, nbad = log.verify_records(image[:len(buf)], heads)
+        if int(nbad.cpu()[0]):
+            raise ValueError(f"{int(nbad.cpu()[0])} physical record(s) fail their checksum: lsbm::log::BatchReader "
+                             "reads such a log")
+    if side:
+        seg = torch.tensor(side, dtype=torch.int64, device=device)
+        src, dst, ln = (seg[:, i].contiguous() for i in range(3))
+        check(lib().lsbm_gather_dev(_ptr(image), _ptr(src), _ptr(ln), len(side), _ptr(image), _ptr(dst),
+                                    _stream_ptr(None)), "lsbm_gather_dev")
+    rec = torch.tensor(records, dtype=torch.int64, device=device).reshape(-1).contiguous() if records else \
+        torch.zeros(0, dtype=torch.int64, device=device)
+    return image, rec
+
+
+def recover_log(image_host, compression=kNoCompression, block_size=4096, restart_interval=16, bits_per_key=None,
+                paranoid=False, device="cuda", stream=None):
+    """RecoverLogFile for a log that fits one memtable: log_records, then flush."""
+    image, records = log_records(image_host, device, stream)
+    return flush(image, records, compression, block_size, restart_interval, bits_per_key, paranoid, stream)
