@@ -138,6 +138,17 @@ MEMTABLE_SIGNATURES = {
     "lsbm_memtable_sort_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
 }
 
+# every symbol include/lsbm_get.h declares
+_i32 = ctypes.c_int32
+GET_SIGNATURES = {
+    "lsbm_lookup_keys_dev": (_int, [_vp, _u64, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "lsbm_memtable_get_dev": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "lsbm_find_file_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "lsbm_save_value_dev": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _i32, _vp, _vp, _vp, _vp,
+                                   _vp]),
+    "lsbm_slices_gather_dev": (_int, [_vp, _u64, _vp, _vp, _i32, _i32, _vp, _u64, _vp, _u64, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -159,7 +170,8 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(BLOCK_SIGNATURES.items())
                                   + list(BLOCK_BUILD_SIGNATURES.items()) + list(MERGE_SIGNATURES.items())
-                                  + list(TABLE_PACK_SIGNATURES.items()) + list(MEMTABLE_SIGNATURES.items())):
+                                  + list(TABLE_PACK_SIGNATURES.items()) + list(MEMTABLE_SIGNATURES.items())
+                                  + list(GET_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)
