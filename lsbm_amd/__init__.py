@@ -17,13 +17,15 @@
                     iteration order as a sort, log image -> Level-0 table file
   lsbm_amd.db       batched DB::Get: LookupKey, MemTable::Get, FindFile, SaveValue, and the chain over
                     memtables and table files (Version.get)
+  lsbm_amd.scan     batched range scans: DBIter's snapshot view of merged entries, Seek / SeekToFirst /
+                    SeekToLast / Next / Prev / status for many range queries at once (Version.view)
 
 The compute lives in lsbm_amd/liblsbm_crc32c.so (hand-written gfx950 HIP
 kernels behind the C ABIs in include/lsbm_crc32c.h, include/lsbm_bloom.h, include/lsbm_snappy.h and
 include/lsbm_block.h, include/lsbm_block_build.h, include/lsbm_merge.h, include/lsbm_table_pack.h,
-include/lsbm_memtable.h, include/lsbm_get.h).
+include/lsbm_memtable.h, include/lsbm_get.h, include/lsbm_iter.h).
 """
 from ._lib import LIB_PATH, LsbmError, lib  # noqa: F401
 
 __all__ = ["LIB_PATH", "LsbmError", "lib", "crc32c", "engine", "table", "log", "bloom", "snappy",
-           "block", "block_build", "merge", "sstable", "memtable", "db"]
+           "block", "block_build", "merge", "sstable", "memtable", "db", "scan"]

@@ -149,6 +149,18 @@ GET_SIGNATURES = {
     "lsbm_slices_gather_dev": (_int, [_vp, _u64, _vp, _vp, _i32, _i32, _vp, _u64, _vp, _u64, _vp, _vp]),
 }
 
+# every symbol include/lsbm_iter.h declares
+ITER_SIGNATURES = {
+    "lsbm_dbiter_scratch_bytes": (_u64, [_u64]),
+    "lsbm_dbiter_plan_dev": (_int, [_vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64,
+                                    _vp]),
+    "lsbm_dbiter_range_dev": (_int, [_vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64,
+                                     _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u64, _vp, _int, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp]),
+    "lsbm_dbiter_emit_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _int, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp,
+                                    _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -171,7 +183,7 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(BLOCK_SIGNATURES.items())
                                   + list(BLOCK_BUILD_SIGNATURES.items()) + list(MERGE_SIGNATURES.items())
                                   + list(TABLE_PACK_SIGNATURES.items()) + list(MEMTABLE_SIGNATURES.items())
-                                  + list(GET_SIGNATURES.items())):
+                                  + list(GET_SIGNATURES.items()) + list(ITER_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)

@@ -22,6 +22,9 @@ torch's current stream).
     Version.for_levels(...)            the probe order of Version::Get
     Version.get(user_keys, key_offsets, snapshot, memtables, verify)
                                        the whole chain
+    Version.view(snapshot, memtables, runs, verify)
+                                       DBImpl::NewIterator: the scan.SnapshotView
+                                       over the memtables and the runs' tables
     status_string(code, user_key)      the reference's Status::ToString()
 
 Keys are a uint8 buffer plus int64 offsets (key i = keys[off[i], off[i+1])).
@@ -373,6 +376,7 @@ class Version:
             return [host[o:o + s] for o, s in pairs], contents, oh
 
         footers = [_decode_footer(d, f"file {f.number}") for d, f in zip(datas, self.files)]
+        self._index_at = [footers[i][1] for i in range(nf)]  # each index block's handle in its file (view)
         # the metaindex blocks: where the filter block is (Table::ReadMeta)
         metas, _, _ = read([(i, footers[i][0]) for i in range(nf)], "metaindex block")
         filter_handle = [None] * nf
@@ -570,3 +574,113 @@ class Version:
             images.append((source, source + 1, contents))
         _status_ok(bad, "Version.get")
         return _collect(verdict, value, where, images)
+
+    def view(self, snapshot, memtables=(), runs=None, verify=True, stream=None):
+        """DBImpl::NewIterator at `snapshot` (lsbm/db_impl.cc:1290-): the
+        scan.SnapshotView over `memtables` (MemTable, in the order given: mem,
+        then imm) and the runs `runs` (indices into self.runs; None: all of
+        them in order), whose scan() answers range queries.
+
+        NewInternalIterator (:1139-1157) is one MergingIterator over the
+        memtables and Version::AddIterators' children; here every data block of
+        the chosen runs' files goes through sstable.read_blocks (as
+        sstable.compact steps 1-2), a run's files' blocks are concatenated in
+        file order into one sorted run (what NewConcatenatingIterator yields),
+        the memtables go first as runs of their own, the value images are
+        concatenated with the slices rebased, and merge.merge (no drop) is the
+        MergingIterator; scan.view then applies DBIter's rule.  A table read
+        that fails raises ValueError with the reference's message (iter_->
+        status()), as does a run whose files overlap (UNSORTED).
+
+        Version::AddIterators (lsbm/version_set.cc:190-210) adds Level 0's
+        deletion part and, for levels 1 and up, both parts -- it leaves out
+        Level 0's insertion part, which Version::Get (:349-) probes.  With
+        runs=None a Version.for_levels tree therefore scans one run more than
+        the reference's iterator sees; for_levels callers who want
+        AddIterators' children pass scan_runs()."""
+        torch = _torch()
+        from . import block, merge, scan, sstable
+        if stream is not None:
+            with torch.cuda.stream(stream):
+                return self.view(snapshot, memtables, runs, verify)
+        dev = self.arena.device
+        chosen = list(range(len(self.runs))) if runs is None else [int(r) for r in runs]
+        if any(not 0 <= r < len(self.runs) for r in chosen):
+            raise ValueError("a run that is not there")
+        if len(memtables) + len(chosen) > merge.MAX_RUNS:
+            raise ValueError(f"at most {merge.MAX_RUNS} memtables and runs")
+        # 1. the data block handles of every chosen run, file after file, moved into the arena
+        base = self.file_base.cpu().tolist()
+        handles, blocks_before = [], [0]
+        for r in chosen:
+            for f in self.runs[r].files:
+                at = (base[f] + self._index_at[f][0], self._index_at[f][1])
+                try:
+                    h = sstable.index_data_handles(self.arena, at, verify).reshape(-1, 2).copy()
+                except ValueError as e:
+                    raise ValueError(f"file {self.files[f].number}: {e}") from None
+                h[:, 0] += base[f]
+                handles.append(h)
+            blocks_before.append(sum(len(h) for h in handles))
+        # 2. ReadBlock of every data block; the entries, one run per chosen run
+        parts_keys, parts_off, parts_val, images, firsts = [], [], [], [], [0]
+        key_base_at, image_base, n_before = 0, 0, 0
+        for mem in memtables:
+            _require_cuda(mem.keys, mem.key_offsets, mem.values, mem.image)
+            vals = mem.values.reshape(-1, 2)
+            parts_keys.append(mem.keys.reshape(-1))
+            parts_off.append(mem.key_offsets[:-1] + key_base_at)
+            parts_val.append(torch.stack([vals[:, 0] + image_base, vals[:, 1]], 1))
+            images.append(mem.image.reshape(-1))
+            key_base_at += mem.keys.numel()
+            image_base += mem.image.numel()
+            n_before += mem.key_offsets.numel() - 1
+            firsts.append(n_before)
+        run_first = torch.tensor(firsts, dtype=torch.int64, device=dev)
+        if handles and sum(len(h) for h in handles):
+            flat = torch.from_numpy(np.concatenate(handles).reshape(-1)).to(dev)
+            contents, out_handles, st = sstable.read_blocks(self.arena, flat, verify)
+            bad = [(b, int(s)) for b, s in enumerate(st.cpu().tolist()) if s != sstable.READ_OK]
+            if bad:
+                raise ValueError(f"data block {bad[0][0]}: {sstable.READ_MESSAGE[bad[0][1]]}")
+            counts, st = block.scan(contents, out_handles)
+            sstable._raise_on(st, "scan")
+            nb = counts.shape[0]
+            entry_base = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+            key_base = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(counts[:, 0], 0, out=entry_base[1:])
+            torch.cumsum(counts[:, 1], 0, out=key_base[1:])
+            keys, key_offsets, values, _, st = block.decode(contents, out_handles, entry_base, key_base)
+            sstable._raise_on(st, "decode")
+            values = values.reshape(-1, 2)
+            parts_keys.append(keys)
+            parts_off.append(key_offsets[:-1] + key_base_at)
+            parts_val.append(torch.stack([values[:, 0] + image_base, values[:, 1]], 1))
+            images.append(contents)
+            key_base_at += keys.numel()
+            table_first = entry_base[torch.tensor(blocks_before[1:], dtype=torch.int64, device=dev)] + n_before
+            run_first = torch.cat([run_first, table_first])
+        else:
+            run_first = torch.cat([run_first, torch.full((len(chosen),), n_before, dtype=torch.int64, device=dev)])
+        end = torch.tensor([key_base_at], dtype=torch.int64, device=dev)
+        all_keys = torch.cat(parts_keys) if parts_keys else _buf(0, torch.uint8, dev)
+        all_off = torch.cat(parts_off + [end]).contiguous()
+        all_val = torch.cat(parts_val).contiguous() if parts_val else _buf(0, torch.int64, dev).view(0, 2)
+        image = torch.cat(images) if images else _buf(0, torch.uint8, dev)
+        if all_keys.numel() == 0:
+            all_keys = _buf(0, torch.uint8, dev)
+        if image.numel() == 0:
+            image = _buf(0, torch.uint8, dev)
+        # 3. the MergingIterator, then DBIter's rule at the snapshot
+        m = merge.merge(all_keys.contiguous(), all_off, all_val, run_first.contiguous(), INTERNAL_KEY)
+        bad = [(r, int(s)) for r, s in enumerate(m.run_status.cpu().tolist()) if s != MERGE_OK]
+        if bad:
+            r, st = bad[0]
+            what = f"memtable {r}" if r < len(memtables) else f"run {chosen[r - len(memtables)]}"
+            raise ValueError(f"{what}: {merge.STATUS_MESSAGE.get(st, st)}")
+        return scan.view(m.keys, m.key_offsets, m.values.reshape(-1).contiguous(), image, snapshot)
+
+    def scan_runs(self):
+        """The runs Version::AddIterators walks, for a Version.for_levels tree:
+        every run but Level 0's insertion part (the one run without a flag)."""
+        return [r for r, run in enumerate(self.runs) if run.flags & (RUN_LEVEL0 | RUN_PRECHECKED)]
