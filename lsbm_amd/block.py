@@ -22,7 +22,7 @@ buffer plus int64 offsets (key i = keys[off[i], off[i+1])).
 from collections import namedtuple
 
 from ._lib import check, lib
-from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
 from .table import kNoCompression, kSnappyCompression
 
 # comparators (include/lsbm_block.h)
@@ -58,18 +58,7 @@ GetResult = namedtuple("GetResult", "state key_len value data_handle")
 
 
 def _check(**ts):
-    """dtype / layout checks for the tensors a kernel will read or write."""
-    torch = _torch()
-    want = {"image": torch.uint8, "keys": torch.uint8, "found": torch.uint8,
-            "status": torch.int32, "state": torch.int32}
-    for name, t in ts.items():
-        if t is None:
-            continue
-        w = want.get(name, torch.int64)
-        if t.dtype != w:
-            raise ValueError(f"{name} must be {w}, got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
+    _check_tensors(ts, u8=("image", "keys", "found"), i32=("status", "state"))
 
 
 def _n_handles(handles):

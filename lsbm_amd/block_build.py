@@ -27,7 +27,7 @@ import numpy as np
 
 from ._lib import check, lib
 from .block import BYTEWISE, INTERNAL_KEY
-from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _check_tensors, _ptr, _raise_on as _raise_on_status, _require_cuda, _stream_ptr, _torch
 from .table import kNoCompression, layout_blocks, seal_blocks
 
 # per-block / per-table status (include/lsbm_block_build.h)
@@ -47,17 +47,7 @@ PlanResult = namedtuple("PlanResult", "block_first block_bytes table_block_first
 
 
 def _check(**ts):
-    """dtype / layout checks for the tensors a kernel will read or write."""
-    torch = _torch()
-    want = {"keys": torch.uint8, "value_image": torch.uint8, "out": torch.uint8}
-    for name, t in ts.items():
-        if t is None:
-            continue
-        w = want.get(name, torch.int64)
-        if t.dtype != w:
-            raise ValueError(f"{name} must be {w}, got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
+    _check_tensors(ts, u8=("keys", "value_image", "out"))
 
 
 def _n_entries(key_offsets, values=None):
@@ -166,9 +156,7 @@ def index_block(keys, key_offsets, block_first, table_block_first, data_handles,
 
 
 def _raise_on(status, what):
-    bad = [int(s) for s in status.cpu().tolist() if s != BUILD_OK]
-    if bad:
-        raise ValueError(f"{what}: {STATUS_MESSAGE.get(bad[0], bad[0])}")
+    _raise_on_status(status, what, BUILD_OK, STATUS_MESSAGE)
 
 
 def footer(metaindex_handle, index_handle):

@@ -6,8 +6,6 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "../../include/lsbm_block_build.h"
 #include "block_build_types.h"
 #include "engine_internal.h"
@@ -19,36 +17,6 @@ hipError_t launch_block_plan(const PlanArgs& a, int entry_grid, int table_wave_g
 hipError_t launch_block_build(const BuildArgs& a, int grid, hipStream_t stream);
 hipError_t launch_index_build(const IndexArgs& a, int grid, hipStream_t stream);
 
-namespace {
-
-// grid-stride: no more workgroups than are resident at once (4 per CU: the
-// build kernels' LDS tiles, 4 x 32 KiB of a CU's 160 KiB)
-int grid_for(int cus, uint64_t items, uint64_t per_wg, uint64_t wgs_per_cu) {
-  const uint64_t wgs = (items + per_wg - 1) / per_wg;
-  return (int)std::max<uint64_t>(1, std::min<uint64_t>(wgs, (uint64_t)cus * wgs_per_cu));
-}
-
-// [p, p + n) and [q, q + m) share a byte
-bool overlap(const void* p, uint64_t n, const void* q, uint64_t m) {
-  if (!p || !q || !n || !m) return false;
-  const uint64_t a = reinterpret_cast<uint64_t>(p), b = reinterpret_cast<uint64_t>(q);
-  return a < b + m && b < a + n;
-}
-
-struct Range {
-  const void* p;
-  uint64_t n;
-};
-
-template <size_t NO, size_t NI>
-bool any_overlap(const Range (&outs)[NO], const Range (&ins)[NI]) {
-  for (const Range& o : outs)
-    for (const Range& i : ins)
-      if (overlap(o.p, o.n, i.p, i.n)) return true;
-  return false;
-}
-
-}  // namespace
 }  // namespace lsbm
 
 using namespace lsbm;
@@ -143,6 +111,7 @@ __attribute__((visibility("default"))) int lsbm_block_build_dev(
   a.out_handles = d_out_handles;
   a.built_bytes = d_built_bytes;
   a.status = d_status;
+  // 4 workgroups per CU: the build kernels' LDS tiles, 4 x 32 KiB of a CU's 160 KiB
   const hipError_t e = launch_block_build(a, grid_for(cus, n_blocks, kBuildWaves, 4), static_cast<hipStream_t>(stream));
   return e == hipSuccess ? LSBM_OK : engine_fail_hip(e, "block_build_kernel");
 }

@@ -35,15 +35,11 @@
 #include <stdint.h>
 
 #include "block_build_types.h"
+#include "device_common.h"  // gcu8, gu8, lu8, u32x4, gu32x4, gptr, gwptr, wave_phase, wave_sum, wave_incl_scan
 
 namespace lsbm {
 namespace {
 
-typedef const __attribute__((address_space(1))) uint8_t* gcu8;
-typedef __attribute__((address_space(1))) uint8_t* gu8;
-typedef __attribute__((address_space(3))) uint8_t* lu8;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) u32x4* gu32x4;
 typedef const __attribute__((address_space(3))) u32x4* lcu32x4;
 
 constexpr uint32_t kSizeTooLarge = 0xffffffffu;  // plan: an entry of 2^32 - 1 bytes or more
@@ -52,30 +48,10 @@ constexpr uint64_t kBytesBad = ~0ull;            // plan: a block with such an e
 constexpr uint64_t kBytesTooLarge = ~0ull - 1;
 constexpr uint64_t kMaxBlock = 1ull << 32;
 
-__device__ __forceinline__ void wave_phase() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ gcu8 gptr(const uint8_t* p, uint64_t off) {
-  return reinterpret_cast<gcu8>(reinterpret_cast<uint64_t>(p) + off);
-}
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
   for (int o = 32; o; o >>= 1) {
     const uint32_t t = (uint32_t)__shfl_xor((int)v, o);
     v = t > v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, uint32_t lane) {
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint64_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
   }
   return v;
 }
@@ -434,7 +410,7 @@ __global__ __launch_bounds__(kBuildThreads) void block_build_kernel(BuildArgs a)
         write_block(tile + phase, a, e0, n, first, fin, lane);
         flush_tile(tile, phase, dst, (uint32_t)fin, lane);
       } else {
-        write_block(reinterpret_cast<gu8>(reinterpret_cast<uint64_t>(a.out) + w_off), a, e0, n, first, fin, lane);
+        write_block(gwptr(a.out, w_off), a, e0, n, first, fin, lane);
       }
     }
     if (lane == 0) {
@@ -579,7 +555,7 @@ __global__ __launch_bounds__(kBuildThreads) void index_build_kernel(IndexArgs a)
         write_index(tile + phase, a, b0, n, first, fin, lane);
         flush_tile(tile, phase, dst, (uint32_t)fin, lane);
       } else {
-        write_index(reinterpret_cast<gu8>(reinterpret_cast<uint64_t>(a.out) + w_off), a, b0, n, first, fin, lane);
+        write_index(gwptr(a.out, w_off), a, b0, n, first, fin, lane);
       }
     }
     if (lane == 0) {

@@ -6,8 +6,6 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "../../include/lsbm_block.h"
 #include "block_types.h"
 #include "engine_internal.h"
@@ -20,17 +18,11 @@ hipError_t launch_block_seek(const BlockSeekArgs& a, int grid, hipStream_t strea
 
 namespace {
 
-// grid-stride: no more workgroups than are resident at once (4 per CU: the
-// walk kernels' LDS tiles, 4 x 32 KiB of a CU's 160 KiB)
-int grid_for(int cus, uint64_t items, uint64_t per_wg, uint64_t wgs_per_cu) {
-  const uint64_t wgs = (items + per_wg - 1) / per_wg;
-  return (int)std::max<uint64_t>(1, std::min<uint64_t>(wgs, (uint64_t)cus * wgs_per_cu));
-}
-
 int walk(BlockWalkArgs& a, bool decode, void* stream) {
   int cus = 0;
   const int rc = engine_current_cus(&cus);
   if (rc != LSBM_OK) return rc;
+  // 4 workgroups per CU: the walk kernels' LDS tiles, 4 x 32 KiB of a CU's 160 KiB
   // (decode's key caches: 48 KiB of LDS per workgroup, 3 per CU)
   const hipError_t e =
       launch_block_walk(a, decode, grid_for(cus, a.n, kBlockWaves, decode ? 3 : 4), static_cast<hipStream_t>(stream));

@@ -27,40 +27,14 @@
 #include <stdint.h>
 
 #include "block_types.h"
+#include "device_common.h"  // gcu8, gu8, lu8, u32x4, gptr, gwptr, wave_phase, wave_sum, wave_incl_scan, varint32
 
 namespace lsbm {
 namespace {
 
-typedef const __attribute__((address_space(1))) uint8_t* gcu8;
-typedef __attribute__((address_space(1))) uint8_t* gu8;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) u32x4* gcu32x4;
-
-__device__ __forceinline__ void wave_phase() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-}
-
 template <class P>
 __device__ __forceinline__ uint32_t le32(P d, uint32_t o) {  // DecodeFixed32, any alignment
   return (uint32_t)d[o] | ((uint32_t)d[o + 1] << 8) | ((uint32_t)d[o + 2] << 16) | ((uint32_t)d[o + 3] << 24);
-}
-
-// GetVarint32Ptr (util/coding.cc:112-129): at most 5 bytes, never past limit;
-// the fifth byte's bits above 2^32 are dropped as the reference's shift does.
-template <class P>
-__device__ __forceinline__ bool varint32(P d, uint32_t& p, uint32_t limit, uint32_t& v) {
-  uint32_t r = 0;
-  for (uint32_t shift = 0; shift <= 28 && p < limit; shift += 7) {
-    const uint32_t byte = d[p++];
-    if (byte & 128u) {
-      r |= (byte & 127u) << shift;
-    } else {
-      v = r | (byte << shift);
-      return true;
-    }
-  }
-  return false;
 }
 
 struct Hdr {
@@ -101,8 +75,6 @@ struct Tot {
 constexpr uint32_t kKeyCache = 64;
 constexpr uint32_t kKeyCacheWave = kKeyCache * 64;
 __device__ __forceinline__ uint32_t kc_idx(uint32_t i) { return (i >> 2) * 256u + (i & 3u); }
-
-typedef __attribute__((address_space(3))) uint8_t* lu8;
 
 // Where a walk's entries go.  Entry t.n of the walk is entry e0 + t.n of the
 // output, its key starts at key byte k0 + t.kb.  The windows' ends are
@@ -173,18 +145,6 @@ __device__ __forceinline__ uint32_t walk_sequential(P d, uint32_t p, uint32_t li
     p = h.kp + h.ns + h.vl;
   }
   return kBlkOk;
-}
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, uint32_t lane) {
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint64_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
 }
 
 // The restart interval of lane `lane` in the chunk starting at interval c0:
@@ -427,7 +387,7 @@ __global__ __launch_bounds__(kBlockThreads) void block_seek_kernel(BlockSeekArgs
     if (off > a.image_size || size64 > a.image_size - off || size64 > 0xffffffffull || size64 < 4) {
       state = kSeekBadContents;
     } else {
-      const gcu8 d = reinterpret_cast<gcu8>(reinterpret_cast<uint64_t>(a.image) + off);
+      const gcu8 d = gptr(a.image, off);
       const uint32_t size = (uint32_t)size64;
       const uint32_t nr = le32(d, size - 4);
       if (nr > (size - 4) / 4) {
@@ -438,7 +398,7 @@ __global__ __launch_bounds__(kBlockThreads) void block_seek_kernel(BlockSeekArgs
         const uint32_t restarts = size - (1 + nr) * 4;
         const uint64_t t0 = a.key_offsets[q], t1 = a.key_offsets[q + 1];
         const uint64_t tlen = t1 >= t0 ? t1 - t0 : 0;
-        const gcu8 t = reinterpret_cast<gcu8>(reinterpret_cast<uint64_t>(a.keys) + t0);
+        const gcu8 t = gptr(a.keys, t0);
         // the found-key window
         uint64_t fo = 0, fcap = 0;
         if (a.found) {
@@ -448,7 +408,7 @@ __global__ __launch_bounds__(kBlockThreads) void block_seek_kernel(BlockSeekArgs
             fcap = f1 - f0;
           }
         }
-        const gu8 fw = reinterpret_cast<gu8>(reinterpret_cast<uint64_t>(a.found) + fo);
+        const gu8 fw = gwptr(a.found, fo);
         bool bad = false;
         // binary search over the restart points (table/block.cc:226-250)
         uint32_t left = 0, right = nr - 1;

@@ -6,8 +6,6 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "../../include/lsbm_bloom.h"
 #include "bloom_types.h"
 #include "engine_internal.h"
@@ -21,11 +19,6 @@ int bloom_build_blocks_per_cu();
 int bloom_probe_blocks_per_cu(uint32_t mode);
 
 namespace {
-
-int grid_for(int cus, uint64_t items, uint64_t per_wg, uint64_t wgs_per_cu) {
-  const uint64_t wgs = (items + per_wg - 1) / per_wg;
-  return (int)std::max<uint64_t>(1, std::min<uint64_t>(wgs, (uint64_t)cus * wgs_per_cu));
-}
 
 int probe(const uint8_t* base, const uint64_t* handles, const uint64_t* data_offsets,
           const void* keys, const uint64_t* key_offsets, uint32_t strip, uint64_t n,

@@ -21,37 +21,8 @@ hipError_t launch_slices_gather(const GatherArgs& a, hipStream_t stream);
 
 namespace {
 
-// [p, p + n) and [q, q + m) share a byte
-bool overlap(const void* p, uint64_t n, const void* q, uint64_t m) {
-  if (!p || !q || !n || !m) return false;
-  const uint64_t a = reinterpret_cast<uint64_t>(p), b = reinterpret_cast<uint64_t>(q);
-  return a < b + m && b < a + n;
-}
-
-struct Range {
-  const void* p;
-  uint64_t n;
-};
-
-// an output shares a byte with an input or with another output
-template <size_t NO, size_t NI>
-bool aliased(const Range (&outs)[NO], const Range (&ins)[NI]) {
-  for (size_t i = 0; i < NO; i++) {
-    for (const Range& in : ins)
-      if (overlap(outs[i].p, outs[i].n, in.p, in.n)) return true;
-    for (size_t j = i + 1; j < NO; j++)
-      if (overlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n)) return true;
-  }
-  return false;
-}
-
 constexpr uint64_t kMaxQueries = 1ull << 31;  // per call
 constexpr uint64_t kMaxEntries = 1ull << 36;  // memtable entries, files, (query, run) pairs
-
-int ready() {
-  int cus = 0;
-  return engine_current_cus(&cus);
-}
 
 }  // namespace
 }  // namespace lsbm
@@ -73,7 +44,7 @@ __attribute__((visibility("default"))) int lsbm_lookup_keys_dev(const uint8_t* d
   const Range ins[] = {{d_user_keys, user_keys_size}, {d_user_offsets, 8 * (n_queries + 1)},
                        {d_snapshots, 8 * n_queries}};
   if (aliased(outs, ins)) return engine_fail(LSBM_ERR_INVALID, "outputs alias inputs");
-  const int rc = ready();
+  const int rc = engine_ready();
   if (rc != LSBM_OK) return rc;
   LookupArgs a = {};
   a.user_keys = d_user_keys;
@@ -104,7 +75,7 @@ __attribute__((visibility("default"))) int lsbm_memtable_get_dev(
   const Range ins[] = {{d_mem_keys, mem_keys_size}, {d_mem_key_offsets, 8 * (n_entries + 1)},
                        {d_mem_values, 16 * n_entries}, {d_keys, keys_size}, {d_key_offsets, 8 * (n_queries + 1)}};
   if (aliased(outs, ins)) return engine_fail(LSBM_ERR_INVALID, "outputs alias inputs");
-  const int rc = ready();
+  const int rc = engine_ready();
   if (rc != LSBM_OK) return rc;
   MemGetArgs a = {};
   a.q = {d_keys, keys_size, d_key_offsets, n_queries, source_id, d_verdict, d_value, d_where, d_status};
@@ -133,7 +104,7 @@ __attribute__((visibility("default"))) int lsbm_find_file_dev(
                        {d_run_first, 8 * (n_runs + 1)}, {d_run_flags, 4 * n_runs}, {d_visible, n_files},
                        {d_keys, keys_size}, {d_key_offsets, 8 * (n_queries + 1)}};
   if (aliased(outs, ins)) return engine_fail(LSBM_ERR_INVALID, "outputs alias inputs");
-  const int rc = ready();
+  const int rc = engine_ready();
   if (rc != LSBM_OK) return rc;
   FindFileArgs a = {};
   a.bounds = d_bounds;
@@ -170,7 +141,7 @@ __attribute__((visibility("default"))) int lsbm_save_value_dev(
                        {d_found_offsets, 8 * (n_queries + 1)}, {d_value_in, 16 * n_queries}, {d_keys, keys_size},
                        {d_key_offsets, 8 * (n_queries + 1)}};
   if (aliased(outs, ins)) return engine_fail(LSBM_ERR_INVALID, "outputs alias inputs");
-  const int rc = ready();
+  const int rc = engine_ready();
   if (rc != LSBM_OK) return rc;
   SaveArgs a = {};
   a.q = {d_keys, keys_size, d_key_offsets, n_queries, source_id, d_verdict, d_value, d_where, d_status};
@@ -198,7 +169,7 @@ __attribute__((visibility("default"))) int lsbm_slices_gather_dev(const uint8_t*
   const Range ins[] = {{d_image, image_size}, {d_slices, 16 * n_queries}, {d_where, 4 * n_queries},
                        {d_out_offsets, 8 * (n_queries + 1)}};
   if (aliased(outs, ins)) return engine_fail(LSBM_ERR_INVALID, "outputs alias inputs");
-  const int rc = ready();
+  const int rc = engine_ready();
   if (rc != LSBM_OK) return rc;
   GatherArgs a = {};
   a.image = d_image;

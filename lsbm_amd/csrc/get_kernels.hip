@@ -26,29 +26,22 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_common.h"  // gcu8, gu8, gptr, gwptr, load8, store8, global_index
 #include "get_types.h"
-#include "key_compare_device.h"  // gcu8, gu8, gptr, load8, bytes_compare
+#include "key_compare_device.h"  // bytes_compare, internal_compare
 
 namespace lsbm {
 namespace {
 
-__device__ __forceinline__ gu8 gwptr(uint8_t* p, uint64_t off) {
-  return reinterpret_cast<gu8>(reinterpret_cast<uint64_t>(p) + off);
-}
-
-__device__ __forceinline__ void store8(gu8 p, uint64_t x) { __builtin_memcpy(p, &x, 8); }
-
-__device__ __forceinline__ uint64_t global_index() { return (uint64_t)blockIdx.x * kGetThreads + threadIdx.x; }
-
 __global__ __launch_bounds__(kGetThreads) void get_offsets_kernel(OffsetsArgs a) {
-  const uint64_t i = global_index();
+  const uint64_t i = global_index<kGetThreads>();
   if (i >= a.n) return;
   const uint64_t lo = a.offsets[i], hi = a.offsets[i + 1];
   if (lo > hi || hi > a.size || hi - lo < a.min_len) atomicOr(a.status, kGetBadInput);
 }
 
 __global__ __launch_bounds__(kGetThreads) void lookup_check_kernel(LookupArgs a) {
-  const uint64_t i = global_index();
+  const uint64_t i = global_index<kGetThreads>();
   if (i > a.n) return;
   const uint64_t lo = a.user_offsets[i];
   bool bad = lo > a.user_size;
@@ -61,7 +54,7 @@ __global__ __launch_bounds__(kGetThreads) void lookup_check_kernel(LookupArgs a)
 }
 
 __global__ __launch_bounds__(kGetThreads) void lookup_keys_kernel(LookupArgs a) {
-  const uint64_t q = global_index();
+  const uint64_t q = global_index<kGetThreads>();
   if (q > a.n || *a.status) return;
   const uint64_t lo = a.user_offsets[q];
   a.key_offsets[q] = lo + 8 * q;
@@ -76,18 +69,8 @@ __global__ __launch_bounds__(kGetThreads) void lookup_keys_kernel(LookupArgs a) 
   store8(dst + len, (seq << 8) | 1u);  // kValueTypeForSeek = kTypeValue
 }
 
-// InternalKeyComparator::Compare of a stored key (at `at`, `len` >= 8 bytes of
-// `buf`) with the lookup key (user key u of ulen bytes, tag): < 0, 0, > 0
-__device__ __forceinline__ int internal_compare(const uint8_t* buf, uint64_t at, uint64_t len, gcu8 u, uint64_t ulen,
-                                                uint64_t tag) {
-  const int c = bytes_compare(gptr(buf, at), len - 8, u, ulen);
-  if (c) return c;
-  const uint64_t t = load8(gptr(buf, at + len - 8));
-  return t > tag ? -1 : (t < tag ? 1 : 0);  // the larger tag sorts first
-}
-
 __global__ __launch_bounds__(kGetThreads) void mem_get_kernel(MemGetArgs a) {
-  const uint64_t q = global_index();
+  const uint64_t q = global_index<kGetThreads>();
   if (q >= a.q.n || *a.q.status || a.q.verdict[q] != kGetUndecided) return;
   const uint64_t ka = a.q.key_offsets[q], ulen = a.q.key_offsets[q + 1] - ka - 8;
   const gcu8 u = gptr(a.q.keys, ka);
@@ -122,7 +105,7 @@ __global__ __launch_bounds__(kGetThreads) void mem_get_kernel(MemGetArgs a) {
 }
 
 __global__ __launch_bounds__(kGetThreads) void run_check_kernel(FindFileArgs a) {
-  const uint64_t r = global_index();
+  const uint64_t r = global_index<kGetThreads>();
   if (r >= a.n_runs) return;
   const uint64_t first = a.run_first[r], last = a.run_first[r + 1];
   if (first > last || last > a.n_files || ((a.run_flags[r] & kRunLevel0) && last - first > 1))
@@ -130,7 +113,7 @@ __global__ __launch_bounds__(kGetThreads) void run_check_kernel(FindFileArgs a) 
 }
 
 __global__ __launch_bounds__(kGetThreads) void find_file_kernel(FindFileArgs a) {
-  const uint64_t idx = global_index();
+  const uint64_t idx = global_index<kGetThreads>();
   if (idx >= a.n * a.n_runs) return;
   const uint64_t q = idx / a.n_runs, r = idx - q * a.n_runs;
   int32_t file = -1;
@@ -168,7 +151,7 @@ __global__ __launch_bounds__(kGetThreads) void find_file_kernel(FindFileArgs a) 
 }
 
 __global__ __launch_bounds__(kGetThreads) void save_check_kernel(SaveArgs a) {
-  const uint64_t q = global_index();
+  const uint64_t q = global_index<kGetThreads>();
   if (q >= a.q.n) return;
   const uint32_t state = a.state[q];
   bool bad = state > kStateMax;
@@ -180,7 +163,7 @@ __global__ __launch_bounds__(kGetThreads) void save_check_kernel(SaveArgs a) {
 }
 
 __global__ __launch_bounds__(kGetThreads) void save_value_kernel(SaveArgs a) {
-  const uint64_t q = global_index();
+  const uint64_t q = global_index<kGetThreads>();
   if (q >= a.q.n || *a.q.status || a.q.verdict[q] != kGetUndecided) return;
   const uint32_t state = a.state[q];
   if (state == kStateNotValid || state == kStateFiltered) return;
@@ -212,7 +195,7 @@ __global__ __launch_bounds__(kGetThreads) void save_value_kernel(SaveArgs a) {
 }
 
 __global__ __launch_bounds__(kGetThreads) void slices_gather_kernel(GatherArgs a) {
-  const uint64_t idx = global_index();
+  const uint64_t idx = global_index<kGetThreads>();
   const uint64_t q = idx / kGatherLanes;
   const uint32_t lane = (uint32_t)(idx % kGatherLanes);
   if (q >= a.n) return;

@@ -19,36 +19,7 @@ hipError_t launch_dbiter_emit(const IterEmitArgs& a, hipStream_t stream);
 
 namespace {
 
-// [p, p + n) and [q, q + m) share a byte
-bool overlap(const void* p, uint64_t n, const void* q, uint64_t m) {
-  if (!p || !q || !n || !m) return false;
-  const uint64_t a = reinterpret_cast<uint64_t>(p), b = reinterpret_cast<uint64_t>(q);
-  return a < b + m && b < a + n;
-}
-
-struct Range {
-  const void* p;
-  uint64_t n;
-};
-
-// an output shares a byte with an input or with another output
-template <size_t NO, size_t NI>
-bool aliased(const Range (&outs)[NO], const Range (&ins)[NI]) {
-  for (size_t i = 0; i < NO; i++) {
-    for (const Range& in : ins)
-      if (overlap(outs[i].p, outs[i].n, in.p, in.n)) return true;
-    for (size_t j = i + 1; j < NO; j++)
-      if (overlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n)) return true;
-  }
-  return false;
-}
-
 uint64_t tiles_of(uint64_t n_entries) { return (n_entries + kIterThreads - 1) / kIterThreads; }
-
-int ready() {
-  int cus = 0;
-  return engine_current_cus(&cus);
-}
 
 }  // namespace
 }  // namespace lsbm
@@ -81,7 +52,7 @@ __attribute__((visibility("default"))) int lsbm_dbiter_plan_dev(
                         {d_scratch, scratch_bytes}};
   const Range ins[] = {{d_keys, keys_size}, {d_key_offsets, 8 * (n_entries + 1)}};
   if (aliased(outs, ins)) return engine_fail(LSBM_ERR_INVALID, "outputs alias inputs");
-  const int rc = ready();
+  const int rc = engine_ready();
   if (rc != LSBM_OK) return rc;
   IterPlanArgs a = {};
   a.e = {d_keys, keys_size, d_key_offsets, n_entries};
@@ -137,7 +108,7 @@ __attribute__((visibility("default"))) int lsbm_dbiter_range_dev(
                        {d_hi_present, n_queries},
                        {d_limits, 8 * n_queries}};
   if (aliased(outs, ins)) return engine_fail(LSBM_ERR_INVALID, "outputs alias inputs");
-  const int rc = ready();
+  const int rc = engine_ready();
   if (rc != LSBM_OK) return rc;
   IterRangeArgs a = {};
   a.e = {d_keys, keys_size, d_key_offsets, n_entries};
@@ -195,7 +166,7 @@ __attribute__((visibility("default"))) int lsbm_dbiter_emit_dev(
                        {d_value_prefix, 8 * (n_live + 1)},
                        {d_image, image_size}};
   if (aliased(outs, ins)) return engine_fail(LSBM_ERR_INVALID, "outputs alias inputs");
-  const int rc = ready();
+  const int rc = engine_ready();
   if (rc != LSBM_OK) return rc;
   IterEmitArgs a = {};
   a.j_begin = d_j_begin;

@@ -44,28 +44,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_common.h"  // gcu8, gu8, gptr, gwptr, load8, store8, wave_phase, wave_incl_scan, global_index
 #include "iter_types.h"
-#include "key_compare_device.h"  // gcu8, gu8, gptr, load8, bytes_compare
+#include "key_compare_device.h"  // bytes_compare, internal_compare
 
 namespace lsbm {
 namespace {
 
 constexpr uint32_t kTypeValue = 1;  // common/dbformat.h; kValueTypeForSeek is the same
-
-__device__ __forceinline__ void wave_phase() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ uint64_t global_index() { return (uint64_t)blockIdx.x * kIterThreads + threadIdx.x; }
-
-__device__ __forceinline__ uint64_t wave_incl_sum(uint64_t v, uint32_t lane) {
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint64_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
 
 __device__ __forceinline__ uint64_t wave_incl_max(uint64_t v, uint32_t lane) {
   for (uint32_t o = 1; o < 64; o <<= 1) {
@@ -81,7 +67,7 @@ __device__ __forceinline__ void block_excl_sum3(const uint64_t (&x)[3], uint64_t
   const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   uint64_t inc[3];
   for (int k = 0; k < 3; k++) {
-    inc[k] = wave_incl_sum(x[k], lane);
+    inc[k] = wave_incl_scan(x[k], lane);
     if (lane == 63) lds[w][k] = inc[k];
   }
   __syncthreads();
@@ -127,19 +113,8 @@ __device__ __forceinline__ void block_max2(uint64_t a, uint64_t b, uint64_t (*ld
   before_b = eb > ob ? eb : ob;
 }
 
-// InternalKeyComparator::Compare of a stored key (at `at`, `len` >= 8 bytes of
-// `buf`) with the lookup key (user key u of ulen bytes, tag), which exists only
-// in registers: < 0, 0, > 0
-__device__ __forceinline__ int internal_compare(const uint8_t* buf, uint64_t at, uint64_t len, gcu8 u, uint64_t ulen,
-                                                uint64_t tag) {
-  const int c = bytes_compare(gptr(buf, at), len - 8, u, ulen);
-  if (c) return c;
-  const uint64_t t = load8(gptr(buf, at + len - 8));
-  return t > tag ? -1 : (t < tag ? 1 : 0);  // the larger tag sorts first
-}
-
 __global__ __launch_bounds__(kIterThreads) void iter_offsets_kernel(IterOffsetsArgs a) {
-  const uint64_t i = global_index();
+  const uint64_t i = global_index<kIterThreads>();
   if (i >= a.n) return;
   const uint64_t lo = a.offsets[i], hi = a.offsets[i + 1];
   if (lo > hi || hi > a.size || hi - lo < a.min_len) atomicMax(a.status, kIterBadInput);
@@ -152,7 +127,7 @@ __device__ __forceinline__ bool key_ok(const IterEntries& e, uint64_t ka, uint64
 }
 
 __global__ __launch_bounds__(kIterThreads) void iter_check_kernel(IterPlanArgs a) {
-  const uint64_t e = global_index();
+  const uint64_t e = global_index<kIterThreads>();
   if (e >= a.e.n) return;
   const uint64_t ka = a.e.key_offsets[e], kb = a.e.key_offsets[e + 1];
   uint32_t st = kIterOk;
@@ -165,7 +140,7 @@ __global__ __launch_bounds__(kIterThreads) void iter_check_kernel(IterPlanArgs a
       int c = bytes_compare(k, kb - ka - 8, s, nb - kb - 8);
       if (c == 0) {
         const uint64_t t = load8(k + (kb - ka - 8)), u = load8(s + (nb - kb - 8));
-        c = t > u ? -1 : (t < u ? 1 : 0);
+        c = t > u ? -1 : (t < u ? 1 : 0);  // (tag_compare, spelled out: it compiles differently here)
       }
       if (c > 0) st = kIterUnsorted;
     }
@@ -234,7 +209,7 @@ __global__ __launch_bounds__(kIterThreads) void iter_flag_kernel(IterPlanArgs a)
 template <bool kMax>
 __device__ __forceinline__ void block_excl1(uint64_t x, uint64_t* lds, uint64_t& before, uint64_t& all) {
   const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const uint64_t inc = kMax ? wave_incl_max(x, lane) : wave_incl_sum(x, lane);
+  const uint64_t inc = kMax ? wave_incl_max(x, lane) : wave_incl_scan(x, lane);
   uint64_t ex = __shfl_up(inc, 1);
   if (lane == 0) ex = 0;
   if (lane == 63) lds[w] = inc;
@@ -350,7 +325,7 @@ __device__ __forceinline__ uint64_t seek_entries(const IterEntries& e, gcu8 u, u
 }
 
 __global__ __launch_bounds__(kIterThreads) void iter_range_kernel(IterRangeArgs a) {
-  const uint64_t q = global_index();
+  const uint64_t q = global_index<kIterThreads>();
   if (q >= a.n_queries || *a.status) return;
   const uint64_t n = a.e.n, ny = a.v.counts[0];
   const uint64_t tag = (a.snapshot << 8) | kTypeValue;
@@ -448,7 +423,7 @@ __device__ __forceinline__ void wave_flat_copy(uint8_t* dst, const uint8_t* src,
     }
     if (q1 - q0 == 8 && q1 <= s_out[l + 1]) {
       const uint64_t x = load8(gptr(src, s_src[l] + (q0 - s_out[l])));
-      __builtin_memcpy(reinterpret_cast<gu8>(reinterpret_cast<uint64_t>(dst) + q0), &x, 8);
+      store8(gwptr(dst, q0), x);
     } else {
       for (uint64_t q = q0; q < q1; q++) {
         while (q >= s_out[l + 1]) l++;  // (q < hi = s_out[cnt]: stops at l < cnt)

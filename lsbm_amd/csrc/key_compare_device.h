@@ -1,25 +1,15 @@
-// key_compare_device.h -- the bytewise key compare the device kernels share
-// (merge_kernels.hip, memtable_kernels.hip): BytewiseComparator::Compare
-// (util/comparator.cc:25-27) over global memory, 8 bytes a step.  Device code
-// only; include after <hip/hip_runtime.h>.
+// key_compare_device.h -- the key order the device kernels share (merge,
+// memtable, get, iter): BytewiseComparator::Compare (util/comparator.cc:25-27)
+// over global memory, 8 bytes a step, and InternalKeyComparator::Compare
+// (common/dbformat.cc) on top of it.  Device code only; include after
+// <hip/hip_runtime.h>.
 #pragma once
 #include <stdint.h>
 
+#include "device_common.h"  // gcu8, gptr, load8
+
 namespace lsbm {
 namespace {
-
-typedef const __attribute__((address_space(1))) uint8_t* gcu8;
-typedef __attribute__((address_space(1))) uint8_t* gu8;
-
-__device__ __forceinline__ gcu8 gptr(const uint8_t* p, uint64_t off) {
-  return reinterpret_cast<gcu8>(reinterpret_cast<uint64_t>(p) + off);
-}
-
-__device__ __forceinline__ uint64_t load8(gcu8 p) {
-  uint64_t x;
-  __builtin_memcpy(&x, p, 8);
-  return x;
-}
 
 // memcmp over the shorter length, then the lengths: < 0, 0, > 0
 __device__ __forceinline__ int bytes_compare(gcu8 a, uint64_t alen, gcu8 b, uint64_t blen) {
@@ -51,6 +41,20 @@ __device__ __forceinline__ int bytes_compare(gcu8 a, uint64_t alen, gcu8 b, uint
     i++;
   }
   return alen < blen ? -1 : (alen > blen ? 1 : 0);
+}
+
+// the tie-break of two internal keys whose user keys are equal, on their
+// 8-byte tags (sequence << 8 | type): the larger tag sorts first
+__device__ __forceinline__ int tag_compare(uint64_t a, uint64_t b) { return a > b ? -1 : (a < b ? 1 : 0); }
+
+// InternalKeyComparator::Compare of a stored key (at `at`, `len` >= 8 bytes of
+// `buf`) with the lookup key (user key u of ulen bytes, tag), which may exist
+// only in registers: < 0, 0, > 0
+__device__ __forceinline__ int internal_compare(const uint8_t* buf, uint64_t at, uint64_t len, gcu8 u, uint64_t ulen,
+                                                uint64_t tag) {
+  const int c = bytes_compare(gptr(buf, at), len - 8, u, ulen);
+  if (c) return c;
+  return tag_compare(load8(gptr(buf, at + len - 8)), tag);
 }
 
 }  // namespace

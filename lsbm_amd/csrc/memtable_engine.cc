@@ -19,26 +19,6 @@ hipError_t launch_memtable_sort(const MemSortArgs& a, hipStream_t stream);
 
 namespace {
 
-// [p, p + n) and [q, q + m) share a byte
-bool overlap(const void* p, uint64_t n, const void* q, uint64_t m) {
-  if (!p || !q || !n || !m) return false;
-  const uint64_t a = reinterpret_cast<uint64_t>(p), b = reinterpret_cast<uint64_t>(q);
-  return a < b + m && b < a + n;
-}
-
-struct Range {
-  const void* p;
-  uint64_t n;
-};
-
-template <size_t NO, size_t NI>
-bool any_overlap(const Range (&outs)[NO], const Range (&ins)[NI]) {
-  for (const Range& o : outs)
-    for (const Range& i : ins)
-      if (overlap(o.p, o.n, i.p, i.n)) return true;
-  return false;
-}
-
 constexpr uint64_t kMaxRecords = 1ull << 36;
 
 uint64_t tiles_of(uint64_t n) { return (n + kMemThreads - 1) / kMemThreads; }

@@ -34,7 +34,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "key_compare_device.h"  // gcu8, gptr, load8, bytes_compare
+#include "device_common.h"       // gcu8, gu8, gptr, gwptr, load8, store8, varint32, wave_incl_scan
+#include "key_compare_device.h"  // bytes_compare
 #include "memtable_types.h"
 
 namespace lsbm {
@@ -45,31 +46,13 @@ constexpr uint32_t kWbHeader = 12;                     // common/write_batch.cc:
 constexpr uint32_t kNoEntry = 0xffffffffu;             // the padding of the last tile: word ~0, sorts last
 constexpr uint32_t kMergeBadInput = 2;                 // LSBM_MERGE_BAD_INPUT
 
-// GetVarint32Ptr (util/coding.cc:112-129) over image[pos, end): at most five
-// bytes, the fifth one's high bits fall off the 32-bit result
-__device__ __forceinline__ bool get_varint32(gcu8 img, uint64_t& pos, uint64_t end, uint32_t& v) {
-  uint32_t result = 0;
-  for (uint32_t shift = 0; shift <= 28 && pos < end; shift += 7) {
-    const uint32_t byte = img[pos++];
-    if (byte & 128) {
-      result |= (byte & 127) << shift;
-    } else {
-      v = result | (byte << shift);
-      return true;
-    }
-  }
-  return false;
-}
-
 // GetLengthPrefixedSlice: the slice is image[at, at + len) and pos moves past it
 __device__ __forceinline__ bool get_slice(gcu8 img, uint64_t& pos, uint64_t end, uint64_t& at, uint32_t& len) {
-  if (!get_varint32(img, pos, end, len) || len > end - pos) return false;
+  if (!varint32(img, pos, end, len) || len > end - pos) return false;
   at = pos;
   pos += len;
   return true;
 }
-
-__device__ __forceinline__ void store8(gu8 p, uint64_t x) { __builtin_memcpy(p, &x, 8); }
 
 template <bool kWrite>
 __device__ __forceinline__ void wb_walk(const WbArgs& a, uint64_t r) {
@@ -120,7 +103,7 @@ __device__ __forceinline__ void wb_walk(const WbArgs& a, uint64_t r) {
           st = kWbNoRoom;
           break;
         }
-        const gu8 dst = reinterpret_cast<gu8>(reinterpret_cast<uint64_t>(a.keys) + k);
+        const gu8 dst = gwptr(a.keys, k);
         uint32_t i = 0;
         for (; i + 8 <= key_len; i += 8) {
           store8(dst + i, load8(img + key_at + i));
@@ -227,7 +210,7 @@ __device__ __forceinline__ bool entry_less(const MemSortArgs& a, uint64_t skip, 
     if (c) return c < 0;
   }
   const uint64_t ta = load8(gptr(a.keys, ka + la - 8)), tb = load8(gptr(a.keys, kb + lb - 8));
-  if (ta != tb) return ta > tb;
+  if (ta != tb) return ta > tb;  // (key_compare_device.h's tag_compare, spelled out: it compiles differently here)
   return ia > ib;
 }
 
@@ -296,15 +279,9 @@ __global__ __launch_bounds__(kMemThreads) void mem_merge_kernel(MemSortArgs a, u
   }
 }
 
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, uint32_t lane) {
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint64_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
 // exclusive sum of v over the workgroup's lanes in lane order, and the total
+// (device_common.h's block_excl_sum adds in another order and moves these
+// kernels' instructions: this copy stays)
 __device__ __forceinline__ void block_excl_scan(uint64_t v, uint64_t* lds, uint64_t& excl, uint64_t& total) {
   const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const uint64_t incl = wave_incl_scan(v, lane);

@@ -35,7 +35,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "key_compare_device.h"  // gcu8, gptr, load8, bytes_compare
+#include "device_common.h"       // gcu8, gptr, gwptr, load8, store8, wave_phase, wave_incl_scan
+#include "key_compare_device.h"  // bytes_compare, tag_compare
 #include "merge_types.h"
 
 namespace lsbm {
@@ -45,26 +46,12 @@ constexpr uint64_t kMaxSequenceNumber = (1ull << 56) - 1;  // common/dbformat.h
 constexpr uint32_t kTypeDeletion = 0, kTypeValue = 1;
 constexpr uint32_t kCmpInternalKey = 1;  // LSBM_CMP_INTERNAL_KEY
 
-__device__ __forceinline__ void wave_phase() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, uint32_t lane) {
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint64_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
 // Compare of the comparator; under the internal-key one both lengths are >= 8
 __device__ __forceinline__ int key_compare(uint32_t cmp, gcu8 a, uint64_t alen, gcu8 b, uint64_t blen) {
   if (cmp != kCmpInternalKey) return bytes_compare(a, alen, b, blen);
   const int c = bytes_compare(a, alen - 8, b, blen - 8);
   if (c) return c;
-  const uint64_t ta = load8(a + (alen - 8)), tb = load8(b + (blen - 8));
-  return ta > tb ? -1 : (ta < tb ? 1 : 0);  // the tag descending (common/dbformat.cc)
+  return tag_compare(load8(a + (alen - 8)), load8(b + (blen - 8)));  // the tag descending (common/dbformat.cc)
 }
 
 // the run that owns entry e < n: the last r with run_first[r] <= e (run_first
@@ -351,7 +338,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_gather_kernel(MergeGather
     }
     if (q1 - q0 == 8 && q1 <= s_out[w][l + 1]) {
       const uint64_t x = load8(gptr(a.e.keys, s_src[w][l] + (q0 - s_out[w][l])));
-      __builtin_memcpy(reinterpret_cast<gu8>(reinterpret_cast<uint64_t>(a.out_keys) + q0), &x, 8);
+      store8(gwptr(a.out_keys, q0), x);
     } else {
       for (uint64_t q = q0; q < q1; q++) {
         while (q >= s_out[w][l + 1]) l++;  // (q < hi = s_out[cnt]: stops at l < cnt)

@@ -31,41 +31,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_common.h"  // gcu8, gu8, u32x4, gcu32x4, gu32x4, block_excl_sum
 #include "table_pack_types.h"
 
 namespace lsbm {
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) uint8_t* gcu8;
-typedef __attribute__((address_space(1))) uint8_t* gu8;
-typedef const __attribute__((address_space(1))) u32x4* gcv4;
-typedef __attribute__((address_space(1))) u32x4* gv4;
-
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, uint32_t lane) {
-  for (uint32_t o = 1; o < 64; o <<= 1) {
-    const uint64_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// exclusive scan of v over the workgroup's lanes; total: the workgroup's sum
-__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* lds, uint64_t& total) {
-  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const uint64_t incl = wave_incl_scan(v, lane);
-  if (lane == 63) lds[w] = incl;
-  __syncthreads();
-  uint64_t base = 0;
-  total = 0;
-  for (uint32_t i = 0; i < kPackWaves; i++) {
-    const uint64_t t = lds[i];
-    if (i < w) base += t;
-    total += t;
-  }
-  __syncthreads();  // (the row is written again by the caller's next round)
-  return base + incl - v;
-}
 
 // ---------------------------------------------------------------- plan
 
@@ -82,8 +52,8 @@ __global__ __launch_bounds__(kPackThreads) void pack_plan_tile_kernel(PackPlanAr
     size = type ? comp : raw;
     v = size + a.gap;
   }
-  uint64_t total;
-  const uint64_t excl = block_excl_scan(v, lds, total);
+  uint64_t excl, total;
+  block_excl_sum<kPackWaves>(v, lds, excl, total);
   if (i < a.n) {
     a.types[i] = (uint8_t)type;
     a.handles[2 * i] = excl;
@@ -99,8 +69,8 @@ __global__ __launch_bounds__(kPackThreads) void pack_scan_tiles_kernel(uint64_t*
   uint64_t carry = 0;
   for (uint64_t base = 0; base < n_tiles; base += kPackThreads) {
     const uint64_t t = base + threadIdx.x;
-    uint64_t total;
-    const uint64_t excl = block_excl_scan(t < n_tiles ? tiles[t] : 0, lds, total);
+    uint64_t excl, total;
+    block_excl_sum<kPackWaves>(t < n_tiles ? tiles[t] : 0, lds, excl, total);
     if (t < n_tiles) tiles[t] = carry + excl;
     carry += total;
   }
@@ -175,8 +145,8 @@ __global__ __launch_bounds__(kPackThreads) void pack_count_kernel(PackArgs a) {
     a.status[i] = b.status;
     if (b.status == kPackOk) pieces = pack_pieces(pack_chunks(b));
   }
-  uint64_t total;
-  const uint64_t excl = block_excl_scan(pieces, lds, total);
+  uint64_t excl, total;
+  block_excl_sum<kPackWaves>(pieces, lds, excl, total);
   if (i < a.n) a.pieces[i] = excl;
   if (threadIdx.x == 0) a.tiles[blockIdx.x] = total;
 }
@@ -279,10 +249,10 @@ __global__ __launch_bounds__(kPackThreads) void pack_move_kernel(PackArgs a) {
           const uint64_t spare = lane_value(s0, (uint32_t)__builtin_ctzll(some));
           u32x4 x[kPackUnroll], y[kPackUnroll];
 #pragma unroll
-          for (int k = 0; k < kPackUnroll; k++) x[k] = *reinterpret_cast<gcv4>(wide[k] ? PACK_S(k) : spare);
+          for (int k = 0; k < kPackUnroll; k++) x[k] = *reinterpret_cast<gcu32x4>(wide[k] ? PACK_S(k) : spare);
           if (sh) {
 #pragma unroll
-            for (int k = 0; k < kPackUnroll; k++) y[k] = *reinterpret_cast<gcv4>((wide[k] ? PACK_S(k) : spare) + kPackChunk);
+            for (int k = 0; k < kPackUnroll; k++) y[k] = *reinterpret_cast<gcu32x4>((wide[k] ? PACK_S(k) : spare) + kPackChunk);
           } else {
 #pragma unroll
             for (int k = 0; k < kPackUnroll; k++) y[k] = x[k];
@@ -299,7 +269,7 @@ __global__ __launch_bounds__(kPackThreads) void pack_move_kernel(PackArgs a) {
             const u32x4 r = {funnel(v0, v1, bits), funnel(v1, v2, bits), funnel(v2, v3, bits), funnel(v3, v4, bits)};
             if (wide[k]) {
               if (PACK_D(k) >= dst && PACK_D(k) + kPackChunk <= end) {
-                *reinterpret_cast<gv4>(PACK_D(k)) = r;
+                *reinterpret_cast<gu32x4>(PACK_D(k)) = r;
               } else {  // the block's head or tail: its bytes one at a time, out of the registers
                 const uint64_t lo = PACK_D(k) > dst ? PACK_D(k) : dst, hi = PACK_D(k) + kPackChunk < end ? PACK_D(k) + kPackChunk : end;
                 const uint64_t r0 = ((uint64_t)r.y << 32) | r.x, r1 = ((uint64_t)r.w << 32) | r.z;

@@ -39,7 +39,7 @@ from ._lib import check, lib
 from .block import (GET_FILTERED, INTERNAL_KEY, SEEK_BAD_CONTENTS, SEEK_BAD_ENTRY, SEEK_BAD_HANDLE, SEEK_NOT_VALID,
                     SEEK_VALID, STATE_MESSAGE)
 from .block_build import FILTER_KEY, kFooterEncodedLength, kTableMagicNumber
-from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _buf, _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
 from .merge import MERGE_BAD_INPUT, MERGE_OK  # noqa: F401 (the status word of every call here)
 from .sstable import GET_BAD_COMPRESSED
 from .table import kBlockTrailerSize
@@ -80,25 +80,9 @@ def status_string(code, user_key=b""):
     raise ValueError(f"unknown status {code}")
 
 
-def _buf(n, dtype, dev, fill=0):
-    """n elements with a non-null address even when n is 0."""
-    torch = _torch()
-    return torch.full((max(n, 1),), fill, dtype=dtype, device=dev)[:n]
-
-
 def _check(**ts):
-    torch = _torch()
-    want = {"keys": torch.uint8, "user_keys": torch.uint8, "image": torch.uint8, "found": torch.uint8,
-            "bounds": torch.uint8, "visible": torch.uint8, "out": torch.uint8, "state": torch.int32,
-            "verdict": torch.int32, "where": torch.int32, "run_flags": torch.int32}
-    for name, t in ts.items():
-        if t is None:
-            continue
-        w = want.get(name, torch.int64)
-        if t.dtype != w:
-            raise ValueError(f"{name} must be {w}, got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
+    _check_tensors(ts, u8=("keys", "user_keys", "image", "found", "bounds", "visible", "out"),
+                   i32=("state", "verdict", "where", "run_flags"))
 
 
 def _status_ok(status, what):

@@ -43,6 +43,36 @@ def _require_cuda(*ts):
             raise ValueError("device tensors required (use crc32c_batch_host for host data)")
 
 
+def _check_tensors(ts, u8=(), i32=()):
+    """dtype / layout checks for the tensors a kernel will read or write: ts
+    maps a name to its tensor (None: not given).  The names in u8 are uint8,
+    those in i32 int32, every other one int64."""
+    torch = _torch()
+    for name, t in ts.items():
+        if t is None:
+            continue
+        w = torch.uint8 if name in u8 else torch.int32 if name in i32 else torch.int64
+        if t.dtype != w:
+            raise ValueError(f"{name} must be {w}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+
+
+def _buf(n, dtype, dev, fill=0):
+    """n elements with a non-null address even when n is 0."""
+    torch = _torch()
+    return torch.full((max(n, 1),), fill, dtype=dtype, device=dev)[:n]
+
+
+def _raise_on(status, what, ok=0, messages=None):
+    """ValueError for the first word of `status` that is not `ok`, in the words
+    of `messages` (status word -> text) where it has them."""
+    bad = [int(s) for s in status.cpu().tolist() if s != ok]
+    if bad:
+        text = f"status {bad[0]}" if messages is None else messages.get(bad[0], bad[0])
+        raise ValueError(f"{what}: {text}")
+
+
 def init(device=0):
     check(lib().lsbm_crc32c_init(int(device)), "lsbm_crc32c_init")
 

@@ -32,7 +32,7 @@ from collections import namedtuple
 import numpy as np
 
 from ._lib import check, lib
-from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
 from .log import kBlockSize, kFirstType, kFullType, kHeaderSize, kLastType, kMiddleType
 from .merge import MERGE_OK, PlanResult
 from .table import kNoCompression
@@ -59,16 +59,7 @@ FlushResult = namedtuple("FlushResult", "image data_handles index_handle smalles
 
 
 def _check(**ts):
-    """dtype / layout checks for the tensors a kernel will read or write."""
-    torch = _torch()
-    for name, t in ts.items():
-        if t is None:
-            continue
-        w = torch.uint8 if name in ("image", "keys") else torch.int64
-        if t.dtype != w:
-            raise ValueError(f"{name} must be {w}, got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
+    _check_tensors(ts, u8=("image", "keys"))
 
 
 def _n_records(records):

@@ -30,7 +30,7 @@ import numpy as np
 
 from ._lib import check, lib
 from .block import BYTEWISE, INTERNAL_KEY
-from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _check_tensors, _ptr, _raise_on, _require_cuda, _stream_ptr, _torch
 
 # per-run status (include/lsbm_merge.h)
 MERGE_OK = 0
@@ -52,16 +52,7 @@ OutputTable = namedtuple("OutputTable", "image data_handles index_handle")
 
 
 def _check(**ts):
-    """dtype / layout checks for the tensors a kernel will read or write."""
-    torch = _torch()
-    for name, t in ts.items():
-        if t is None:
-            continue
-        w = torch.uint8 if name in ("keys", "out_keys") else torch.int64
-        if t.dtype != w:
-            raise ValueError(f"{name} must be {w}, got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
+    _check_tensors(ts, u8=("keys", "out_keys"))
 
 
 def _flags(cmp, drop, smallest_snapshot, bottom_level):
@@ -210,12 +201,6 @@ def index_data_handles(image, index_handle):
         s, _ = _get_varint64(buf, p)
         out += [o, s]
     return np.array(out, dtype=np.int64)
-
-
-def _raise_on(status, what):
-    bad = [int(s) for s in status.cpu().tolist() if s != 0]
-    if bad:
-        raise ValueError(f"{what}: status {bad[0]}")
 
 
 def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None, cmp=INTERNAL_KEY, drop=False,

@@ -37,7 +37,7 @@ Prev() while key() >= lo; both stop after `limit` entries.
 from collections import namedtuple
 
 from ._lib import check, lib
-from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _buf, _check_tensors, _ptr, _raise_on as _raise_on_status, _require_cuda, _stream_ptr, _torch
 from .merge import MERGE_BAD_INPUT, MERGE_NO_ROOM, MERGE_OK, MERGE_UNSORTED, PlanResult, kMaxSequenceNumber
 from . import merge as _merge
 
@@ -66,29 +66,12 @@ def status_string(code):
     raise ValueError(f"unknown status {code}")
 
 
-def _buf(n, dtype, dev, fill=0):
-    """n elements with a non-null address even when n is 0."""
-    torch = _torch()
-    return torch.full((max(n, 1),), fill, dtype=dtype, device=dev)[:n]
-
-
 def _check(**ts):
-    torch = _torch()
-    u8 = ("keys", "lo", "hi", "lo_present", "hi_present", "value_image")
-    for name, t in ts.items():
-        if t is None:
-            continue
-        w = torch.uint8 if name in u8 else torch.int64
-        if t.dtype != w:
-            raise ValueError(f"{name} must be {w}, got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
+    _check_tensors(ts, u8=("keys", "lo", "hi", "lo_present", "hi_present", "value_image"))
 
 
 def _raise_on(status, what):
-    st = int(status.cpu()[0])
-    if st != MERGE_OK:
-        raise ValueError(f"{what}: {STATUS_MESSAGE.get(st, st)}")
+    _raise_on_status(status, what, MERGE_OK, STATUS_MESSAGE)  # (one status word per call)
 
 
 def _snapshot(snapshot):

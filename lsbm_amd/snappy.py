@@ -18,7 +18,7 @@ out; every call enqueues on `stream` (default: torch's current stream).
 Blocks are a uint8 buffer plus int64 offsets (block i = data[off[i], off[i+1])).
 """
 from ._lib import check, lib
-from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
 
 # The most a snappy stream of c bytes can expand to: a 3-byte copy tag emits
 # at most 64 bytes (21.3x).  A preamble claiming more cannot be met, so
@@ -27,17 +27,7 @@ MAX_EXPANSION = 22
 
 
 def _check(n_plus_1=None, **ts):
-    """dtype / layout checks for the tensors a kernel will read or write."""
-    torch = _torch()
-    want = {"data": torch.uint8, "out": torch.uint8, "ok": torch.uint8, "offsets": torch.int64,
-            "out_offsets": torch.int64, "out_len": torch.int64, "n_bad": torch.int32}
-    for name, t in ts.items():
-        if t is None:
-            continue
-        if t.dtype != want[name]:
-            raise ValueError(f"{name} must be {want[name]}, got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
+    _check_tensors(ts, u8=("data", "out", "ok"), i32=("n_bad",))
     if n_plus_1 is not None and ts.get("out_offsets") is not None and ts["out_offsets"].numel() != n_plus_1:
         raise ValueError("out_offsets must have n + 1 entries")
 

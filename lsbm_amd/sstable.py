@@ -29,7 +29,7 @@ import numpy as np
 from ._lib import check, lib
 from .block import (BYTEWISE, GET_BAD_CHECKSUM, GET_BAD_TYPE, GET_FILTERED, INTERNAL_KEY, SEEK_BAD_HANDLE,
                     SEEK_VALID)
-from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _ptr, _raise_on, _require_cuda, _stream_ptr, _torch
 from .merge import OutputTable
 from .table import kBlockTrailerSize, kNoCompression, kSnappyCompression, seal_blocks
 
@@ -257,12 +257,6 @@ def read_blocks(image, handles, verify=True, max_bytes=1 << 30, stream=None):
 
 
 # ---------------------------------------------------------------- the writer
-
-
-def _raise_on(status, what):
-    bad = [int(s) for s in status.cpu().tolist() if s != 0]
-    if bad:
-        raise ValueError(f"{what}: status {bad[0]}")
 
 
 def _offsets_of(sizes, dev):
