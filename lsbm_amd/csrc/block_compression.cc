@@ -12,24 +12,11 @@
 
 #include "../../include/lsbm_crc32c.h"
 #include "../../include/lsbm_snappy.h"
-#include "host_session.h"
+#include "host_staging.h"
 
 namespace lsbm {
 
 namespace {
-
-Status check_offsets(const uint64_t* offsets, size_t n) {
-  for (size_t i = 0; i < n; i++)
-    if (offsets[i + 1] < offsets[i]) return Status::InvalidArgument("offsets must not decrease");
-  return Status::OK();
-}
-
-// Rebase offsets[0..n] to start at 0 (the staged copy starts at offsets[0]).
-std::vector<uint64_t> rebased(const uint64_t* offsets, size_t n) {
-  std::vector<uint64_t> r(n + 1);
-  for (size_t i = 0; i <= n; i++) r[i] = offsets[i] - offsets[0];
-  return r;
-}
 
 // The most a snappy stream of c bytes can expand to: its largest tag ratio
 // is a 3-byte copy emitting 64 bytes (21.3x).  A preamble claiming more
@@ -54,27 +41,23 @@ Status CompressBlocks(int device, const char* raw, const uint64_t* offsets, size
   std::vector<uint64_t> cap(n + 1, 0);  // output slots of MaxCompressedLength bytes
   for (size_t i = 0; i < n; i++) cap[i + 1] = cap[i] + lsbm_snappy_max_compressed_length(off[i + 1] - off[i]);
 
-  SessionLease ss;
-  s = ss.Open(device);
+  Staging st;
+  s = st.Open(device);
   if (!s.ok()) return s;
-  const hipStream_t st = ss->stream();
-  void *d_raw, *d_off, *d_cap, *d_comp, *d_len;
-  hipError_t e = ss->scratch(0, total, &d_raw);
-  if (e == hipSuccess) e = ss->scratch(1, (n + 1) * sizeof(uint64_t), &d_off);
-  if (e == hipSuccess) e = ss->scratch(2, (n + 1) * sizeof(uint64_t), &d_cap);
-  if (e == hipSuccess) e = ss->scratch(3, cap[n], &d_comp);
-  if (e == hipSuccess) e = ss->scratch(4, n * sizeof(uint64_t), &d_len);
-  if (e == hipSuccess) e = ss->upload(d_raw, raw + offsets[0], total);
-  if (e == hipSuccess) e = ss->upload(d_off, off.data(), (n + 1) * sizeof(uint64_t));
-  if (e == hipSuccess) e = ss->upload(d_cap, cap.data(), (n + 1) * sizeof(uint64_t));
-  if (e != hipSuccess) return hip_status(e, "staging");
-  if (lsbm_snappy_compress_dev(d_raw, static_cast<const uint64_t*>(d_off), n, static_cast<uint8_t*>(d_comp),
-                               static_cast<const uint64_t*>(d_cap), static_cast<uint64_t*>(d_len),
-                               st) != LSBM_OK)
+  uint8_t* d_raw = st.buf<uint8_t>(0, total);
+  uint64_t* d_off = st.buf<uint64_t>(1, n + 1);
+  uint64_t* d_cap = st.buf<uint64_t>(2, n + 1);
+  uint8_t* d_comp = st.buf<uint8_t>(3, cap[n]);
+  uint64_t* d_len = st.buf<uint64_t>(4, n);
+  st.put(d_raw, raw + offsets[0], total);
+  st.put(d_off, off.data(), n + 1);
+  st.put(d_cap, cap.data(), n + 1);
+  if (!st.ok()) return st.status("staging");
+  if (lsbm_snappy_compress_dev(d_raw, d_off, n, d_comp, d_cap, d_len, st.stream()) != LSBM_OK)
     return Status::IOError(lsbm_crc32c_last_error());
   std::vector<uint64_t> clen(n);
-  e = ss->download(clen.data(), d_len, n * sizeof(uint64_t));
-  if (e != hipSuccess) return hip_status(e, "compress");
+  st.get(clen.data(), d_len, n);
+  if (!st.ok()) return st.status("compress");
 
   // WriteBlock's rule (table/table_builder.cc:187-188), block by block: only
   // the blocks kept compressed have their bytes gathered and brought back
@@ -89,18 +72,16 @@ Status CompressBlocks(int device, const char* raw, const uint64_t* offsets, size
   }
   std::string comp(dense[n], '\0');
   if (dense[n]) {
-    void *d_keep, *d_dense, *d_packed;
-    e = ss->scratch(4, n * sizeof(uint64_t), &d_keep);  // (d_len is no longer needed)
-    if (e == hipSuccess) e = ss->scratch(5, (n + 1) * sizeof(uint64_t), &d_dense);
-    if (e == hipSuccess) e = ss->scratch(6, dense[n], &d_packed);
-    if (e == hipSuccess) e = ss->upload(d_keep, keep_len.data(), n * sizeof(uint64_t));
-    if (e == hipSuccess) e = ss->upload(d_dense, dense.data(), (n + 1) * sizeof(uint64_t));
-    if (e != hipSuccess) return hip_status(e, "staging");
-    if (lsbm_gather_dev(d_comp, static_cast<const uint64_t*>(d_cap), static_cast<const uint64_t*>(d_keep), n,
-                        d_packed, static_cast<const uint64_t*>(d_dense), st) != LSBM_OK)
+    uint64_t* d_keep = st.buf<uint64_t>(4, n);  // (d_len is no longer needed)
+    uint64_t* d_dense = st.buf<uint64_t>(5, n + 1);
+    uint8_t* d_packed = st.buf<uint8_t>(6, dense[n]);
+    st.put(d_keep, keep_len.data(), n);
+    st.put(d_dense, dense.data(), n + 1);
+    if (!st.ok()) return st.status("staging");
+    if (lsbm_gather_dev(d_comp, d_cap, d_keep, n, d_packed, d_dense, st.stream()) != LSBM_OK)
       return Status::IOError(lsbm_crc32c_last_error());
-    e = ss->download(&comp[0], d_packed, dense[n]);
-    if (e != hipSuccess) return hip_status(e, "compress");
+    st.get(&comp[0], d_packed, dense[n]);
+    if (!st.ok()) return st.status("compress");
   }
   out_offsets->resize(n + 1);
   out->reserve(total);
@@ -143,44 +124,37 @@ Status UncompressBlocks(int device, const char* data, const uint64_t* offsets, c
     std::string packed;
     packed.reserve(coff[m]);
     for (size_t j = 0; j < m; j++) packed.append(data + offsets[idx[j]], offsets[idx[j] + 1] - offsets[idx[j]]);
-    SessionLease ss;
-    s = ss.Open(device);
+    Staging st;
+    s = st.Open(device);
     if (!s.ok()) return s;
-    const hipStream_t st = ss->stream();
-    void *d_comp, *d_coff, *d_ulen, *d_ok;
-    hipError_t e = ss->scratch(0, coff[m], &d_comp);
-    if (e == hipSuccess) e = ss->scratch(1, (m + 1) * sizeof(uint64_t), &d_coff);
-    if (e == hipSuccess) e = ss->scratch(2, m * sizeof(uint64_t), &d_ulen);
-    if (e == hipSuccess) e = ss->scratch(3, m, &d_ok);
-    if (e == hipSuccess) e = ss->upload(d_comp, packed.data(), coff[m]);
-    if (e == hipSuccess) e = ss->upload(d_coff, coff.data(), (m + 1) * sizeof(uint64_t));
-    if (e != hipSuccess) return hip_status(e, "staging");
+    uint8_t* d_comp = st.buf<uint8_t>(0, coff[m]);
+    uint64_t* d_coff = st.buf<uint64_t>(1, m + 1);
+    uint64_t* d_ulen = st.buf<uint64_t>(2, m);
+    uint8_t* d_ok = st.buf<uint8_t>(3, m);
+    st.put(d_comp, packed.data(), coff[m]);
+    st.put(d_coff, coff.data(), m + 1);
+    if (!st.ok()) return st.status("staging");
     // GetUncompressedLength sizes the output windows
-    if (lsbm_snappy_uncompressed_length_dev(d_comp, static_cast<const uint64_t*>(d_coff), m,
-                                            static_cast<uint64_t*>(d_ulen), static_cast<uint8_t*>(d_ok),
-                                            st) != LSBM_OK)
+    if (lsbm_snappy_uncompressed_length_dev(d_comp, d_coff, m, d_ulen, d_ok, st.stream()) != LSBM_OK)
       return Status::IOError(lsbm_crc32c_last_error());
-    e = ss->download(ulen.data(), d_ulen, m * sizeof(uint64_t));
-    if (e == hipSuccess) e = ss->download(len_ok.data(), d_ok, m);
-    if (e != hipSuccess) return hip_status(e, "uncompressed length");
+    st.get(ulen.data(), d_ulen, m);
+    st.get(len_ok.data(), d_ok, m);
+    if (!st.ok()) return st.status("uncompressed length");
     for (size_t j = 0; j < m; j++) {
       // a preamble no stream of this length can meet fails now, with no window
       if (len_ok[j] && ulen[j] > kMaxExpansion * (coff[j + 1] - coff[j])) len_ok[j] = 0;
       uoff[j + 1] = uoff[j] + (len_ok[j] ? ulen[j] : 0);
     }
-    void *d_out, *d_uoff;
-    e = ss->scratch(4, uoff[m], &d_out);
-    if (e == hipSuccess) e = ss->scratch(5, (m + 1) * sizeof(uint64_t), &d_uoff);
-    if (e == hipSuccess) e = ss->upload(d_uoff, uoff.data(), (m + 1) * sizeof(uint64_t));
-    if (e != hipSuccess) return hip_status(e, "staging");
-    if (lsbm_snappy_uncompress_dev(d_comp, static_cast<const uint64_t*>(d_coff), m,
-                                   static_cast<uint8_t*>(d_out), static_cast<const uint64_t*>(d_uoff),
-                                   static_cast<uint8_t*>(d_ok), nullptr, st) != LSBM_OK)
+    uint8_t* d_out = st.buf<uint8_t>(4, uoff[m]);
+    uint64_t* d_uoff = st.buf<uint64_t>(5, m + 1);
+    st.put(d_uoff, uoff.data(), m + 1);
+    if (!st.ok()) return st.status("staging");
+    if (lsbm_snappy_uncompress_dev(d_comp, d_coff, m, d_out, d_uoff, d_ok, nullptr, st.stream()) != LSBM_OK)
       return Status::IOError(lsbm_crc32c_last_error());
     dec.assign(uoff[m], '\0');
-    e = ss->download(dec_ok.data(), d_ok, m);
-    if (e == hipSuccess && uoff[m]) e = ss->download(&dec[0], d_out, uoff[m]);
-    if (e != hipSuccess) return hip_status(e, "uncompress");
+    st.get(dec_ok.data(), d_ok, m);
+    st.get(&dec[0], d_out, uoff[m]);
+    if (!st.ok()) return st.status("uncompress");
   }
 
   // assemble in block order; the first failing block names the status

@@ -10,7 +10,7 @@
 
 #include "../../include/lsbm_block.h"
 #include "../../include/lsbm_crc32c.h"
-#include "host_session.h"
+#include "host_staging.h"
 
 namespace lsbm {
 
@@ -34,32 +34,32 @@ Status seek_status(uint32_t s) {
   }
 }
 
+struct Image {
+  uint8_t* image;
+  uint64_t* handles;
+};
+
 // image and handles on the device (scratch 0 and 1)
-Status stage_image(SessionLease& ss, const char* image, size_t image_size, const uint64_t* handles, size_t n,
-                   void** d_image, void** d_handles) {
-  hipError_t e = ss->scratch(0, image_size ? image_size : 1, d_image);
-  if (e == hipSuccess) e = ss->scratch(1, 2 * n * sizeof(uint64_t), d_handles);
-  if (e == hipSuccess && image_size) e = ss->upload(*d_image, image, image_size);
-  if (e == hipSuccess) e = ss->upload(*d_handles, handles, 2 * n * sizeof(uint64_t));
-  return e == hipSuccess ? Status::OK() : hip_status(e, "staging");
+Image stage_image(Staging& st, const char* image, size_t image_size, const uint64_t* handles, size_t n) {
+  const Image d = {st.buf<uint8_t>(0, image_size), st.buf<uint64_t>(1, 2 * n)};
+  st.put(d.image, image, image_size);
+  st.put(d.handles, handles, 2 * n);
+  return d;
 }
 
 // lsbm_block_scan_dev into host vectors (scratch 2 and 3)
-Status scan_staged(SessionLease& ss, const void* d_image, size_t image_size, const void* d_handles, size_t n,
-                   std::vector<uint64_t>* counts, std::vector<uint32_t>* statuses) {
-  void *d_counts, *d_status;
-  hipError_t e = ss->scratch(2, 3 * n * sizeof(uint64_t), &d_counts);
-  if (e == hipSuccess) e = ss->scratch(3, n * sizeof(uint32_t), &d_status);
-  if (e != hipSuccess) return hip_status(e, "staging");
-  if (lsbm_block_scan_dev(static_cast<const uint8_t*>(d_image), image_size, static_cast<const uint64_t*>(d_handles), n,
-                          static_cast<uint64_t*>(d_counts), static_cast<uint32_t*>(d_status),
-                          ss->stream()) != LSBM_OK)
+Status scan_staged(Staging& st, const Image& d, size_t image_size, size_t n, std::vector<uint64_t>* counts,
+                   std::vector<uint32_t>* statuses) {
+  uint64_t* d_counts = st.buf<uint64_t>(2, 3 * n);
+  uint32_t* d_status = st.buf<uint32_t>(3, n);
+  if (!st.ok()) return st.status("staging");
+  if (lsbm_block_scan_dev(d.image, image_size, d.handles, n, d_counts, d_status, st.stream()) != LSBM_OK)
     return Status::IOError(lsbm_crc32c_last_error());
   counts->resize(3 * n);
   statuses->resize(n);
-  e = ss->download(counts->data(), d_counts, 3 * n * sizeof(uint64_t));
-  if (e == hipSuccess) e = ss->download(statuses->data(), d_status, n * sizeof(uint32_t));
-  return e == hipSuccess ? Status::OK() : hip_status(e, "block scan");
+  st.get(counts->data(), d_counts, 3 * n);
+  st.get(statuses->data(), d_status, n);
+  return st.ok() ? Status::OK() : st.status("block scan");
 }
 
 Status first_failure(const std::vector<uint32_t>& statuses) {
@@ -77,14 +77,13 @@ Status ScanBlocks(int device, const char* image, size_t image_size, const uint64
   statuses->clear();
   if (n == 0) return Status::OK();
   if (!handles || (!image && image_size)) return Status::InvalidArgument("null pointer");
-  SessionLease ss;
-  Status s = ss.Open(device);
+  Staging st;
+  Status s = st.Open(device);
   if (!s.ok()) return s;
-  void *d_image, *d_handles;
-  s = stage_image(ss, image, image_size, handles, n, &d_image, &d_handles);
-  if (!s.ok()) return s;
+  const Image d = stage_image(st, image, image_size, handles, n);
+  if (!st.ok()) return st.status("staging");
   std::vector<uint64_t> c;
-  s = scan_staged(ss, d_image, image_size, d_handles, n, &c, statuses);
+  s = scan_staged(st, d, image_size, n, &c, statuses);
   if (!s.ok()) return s;
   counts->resize(n);
   for (size_t i = 0; i < n; i++) (*counts)[i] = BlockCounts{c[3 * i], c[3 * i + 1], c[3 * i + 2]};
@@ -102,15 +101,14 @@ Status DecodeBlocks(int device, const char* image, size_t image_size, const uint
   statuses->clear();
   if (n == 0) return Status::OK();
   if (!handles || (!image && image_size)) return Status::InvalidArgument("null pointer");
-  SessionLease ss;
-  Status s = ss.Open(device);
+  Staging st;
+  Status s = st.Open(device);
   if (!s.ok()) return s;
-  void *d_image, *d_handles;
-  s = stage_image(ss, image, image_size, handles, n, &d_image, &d_handles);
-  if (!s.ok()) return s;
+  const Image d = stage_image(st, image, image_size, handles, n);
+  if (!st.ok()) return st.status("staging");
   std::vector<uint64_t> c;
   std::vector<uint32_t> scanned;
-  s = scan_staged(ss, d_image, image_size, d_handles, n, &c, &scanned);
+  s = scan_staged(st, d, image_size, n, &c, &scanned);
   if (!s.ok()) return s;
   // the windows: running sums of the scan's counts
   std::vector<uint64_t> ebase(n + 1, 0), kbase(n + 1, 0);
@@ -119,32 +117,29 @@ Status DecodeBlocks(int device, const char* image, size_t image_size, const uint
     kbase[i + 1] = kbase[i] + c[3 * i + 1];
   }
   const uint64_t ne = ebase[n], nk = kbase[n];
-  void *d_ebase, *d_kbase, *d_keys, *d_koff, *d_values, *d_status;
-  hipError_t e = ss->scratch(2, 2 * (n + 1) * sizeof(uint64_t), &d_ebase);
-  if (e == hipSuccess) e = ss->scratch(3, n * sizeof(uint32_t), &d_status);
-  if (e == hipSuccess) e = ss->scratch(4, nk ? nk : 1, &d_keys);
-  if (e == hipSuccess) e = ss->scratch(5, (ne + 1) * sizeof(uint64_t), &d_koff);
-  if (e == hipSuccess) e = ss->scratch(6, (2 * ne + 1) * sizeof(uint64_t), &d_values);
-  if (e != hipSuccess) return hip_status(e, "staging");
-  d_kbase = static_cast<uint64_t*>(d_ebase) + (n + 1);
-  e = ss->upload(d_ebase, ebase.data(), (n + 1) * sizeof(uint64_t));
-  if (e == hipSuccess) e = ss->upload(d_kbase, kbase.data(), (n + 1) * sizeof(uint64_t));
-  if (e != hipSuccess) return hip_status(e, "staging");
-  if (lsbm_block_decode_dev(static_cast<const uint8_t*>(d_image), image_size, static_cast<const uint64_t*>(d_handles),
-                            n, static_cast<const uint64_t*>(d_ebase), static_cast<const uint64_t*>(d_kbase),
-                            static_cast<uint8_t*>(d_keys), nk, static_cast<uint64_t*>(d_koff),
-                            static_cast<uint64_t*>(d_values), ne, nullptr, static_cast<uint32_t*>(d_status),
-                            ss->stream()) != LSBM_OK)
+  Packed bases;  // one buffer: entry_base[n+1] key_base[n+1]
+  const auto f_ebase = bases.add<uint64_t>(n + 1), f_kbase = bases.add<uint64_t>(n + 1);
+  uint8_t* d_bases = st.buf<uint8_t>(2, bases.bytes());
+  uint32_t* d_status = st.buf<uint32_t>(3, n);
+  uint8_t* d_keys = st.buf<uint8_t>(4, nk);
+  uint64_t* d_koff = st.buf<uint64_t>(5, ne + 1);
+  uint64_t* d_values = st.buf<uint64_t>(6, 2 * ne + 1);
+  if (!st.ok()) return st.status("staging");
+  st.put(f_ebase.in(d_bases), ebase.data(), n + 1);
+  st.put(f_kbase.in(d_bases), kbase.data(), n + 1);
+  if (!st.ok()) return st.status("staging");
+  if (lsbm_block_decode_dev(d.image, image_size, d.handles, n, f_ebase.in(d_bases), f_kbase.in(d_bases), d_keys, nk,
+                            d_koff, d_values, ne, nullptr, d_status, st.stream()) != LSBM_OK)
     return Status::IOError(lsbm_crc32c_last_error());
   keys->assign(nk, '\0');
   key_offsets->assign(ne + 1, 0);
   values->assign(2 * ne, 0);
   statuses->resize(n);
-  e = ss->download(statuses->data(), d_status, n * sizeof(uint32_t));
-  if (e == hipSuccess && nk) e = ss->download(&(*keys)[0], d_keys, nk);
-  if (e == hipSuccess) e = ss->download(key_offsets->data(), d_koff, (ne + 1) * sizeof(uint64_t));
-  if (e == hipSuccess && ne) e = ss->download(values->data(), d_values, 2 * ne * sizeof(uint64_t));
-  if (e != hipSuccess) return hip_status(e, "block decode");
+  st.get(statuses->data(), d_status, n);
+  st.get(&(*keys)[0], d_keys, nk);
+  st.get(key_offsets->data(), d_koff, ne + 1);
+  st.get(values->data(), d_values, 2 * ne);
+  if (!st.ok()) return st.status("block decode");
   *entry_first = ebase;
   return first_failure(*statuses);
 }
@@ -158,65 +153,62 @@ Status SeekBlocks(int device, const char* image, size_t image_size, const uint64
   if (found_keys) found_keys->clear();
   if (n == 0) return Status::OK();
   if (!handles || !target_offsets || (!image && image_size)) return Status::InvalidArgument("null pointer");
-  for (size_t i = 0; i < n; i++)
-    if (target_offsets[i + 1] < target_offsets[i]) return Status::InvalidArgument("offsets must not decrease");
-  const uint64_t t0 = target_offsets[0], tbytes = target_offsets[n] - t0;
+  Status s = check_offsets(target_offsets, n);
+  if (!s.ok()) return s;
+  const std::vector<uint64_t> toff = rebased(target_offsets, n);
+  const uint64_t tbytes = toff[n];
   if (tbytes && !targets) return Status::InvalidArgument("null pointer");
-  std::vector<uint64_t> toff(n + 1);
-  for (size_t i = 0; i <= n; i++) toff[i] = target_offsets[i] - t0;
 
-  SessionLease ss;
-  Status s = ss.Open(device);
+  Staging st;
+  s = st.Open(device);
   if (!s.ok()) return s;
-  void *d_image, *d_handles, *d_targets, *d_toff, *d_out;
-  s = stage_image(ss, image, image_size, handles, n, &d_image, &d_handles);
-  if (!s.ok()) return s;
-  // results, one buffer: pos[n] key_len[n] value[2n] handle[2n] (u64), state[n] (u32)
-  const size_t out_bytes = 6 * n * sizeof(uint64_t) + n * sizeof(uint32_t);
-  hipError_t e = ss->scratch(2, tbytes ? tbytes : 1, &d_targets);
-  if (e == hipSuccess) e = ss->scratch(3, (n + 1) * sizeof(uint64_t), &d_toff);
-  if (e == hipSuccess) e = ss->scratch(4, out_bytes, &d_out);
-  if (e == hipSuccess && tbytes) e = ss->upload(d_targets, targets + t0, tbytes);
-  if (e == hipSuccess) e = ss->upload(d_toff, toff.data(), (n + 1) * sizeof(uint64_t));
-  if (e != hipSuccess) return hip_status(e, "staging");
-  uint64_t* d_pos = static_cast<uint64_t*>(d_out);
-  uint64_t *d_klen = d_pos + n, *d_value = d_pos + 2 * n, *d_hout = d_pos + 4 * n;
-  uint32_t* d_state = reinterpret_cast<uint32_t*>(d_pos + 6 * n);
+  const Image d = stage_image(st, image, image_size, handles, n);
+  if (!st.ok()) return st.status("staging");
+  Packed res;  // results, one buffer: pos[n] key_len[n] value[2n] handle[2n] (u64), state[n] (u32)
+  const auto f_pos = res.add<uint64_t>(n), f_klen = res.add<uint64_t>(n), f_value = res.add<uint64_t>(2 * n);
+  const auto f_handle = res.add<uint64_t>(2 * n);
+  const auto f_state = res.add<uint32_t>(n);
+  uint8_t* d_targets = st.buf<uint8_t>(2, tbytes);
+  uint64_t* d_toff = st.buf<uint64_t>(3, n + 1);
+  uint8_t* d_out = st.buf<uint8_t>(4, res.bytes());
+  st.put(d_targets, targets + target_offsets[0], tbytes);
+  st.put(d_toff, toff.data(), n + 1);
+  if (!st.ok()) return st.status("staging");
   const uint32_t flags = value_is_handle ? LSBM_SEEK_VALUE_IS_HANDLE : 0u;
-  std::vector<uint8_t> out(out_bytes);
+  std::vector<uint8_t> out(res.bytes());
   std::vector<uint64_t> foff(n + 1, 0);
   std::string found;
   // found keys: a first Seek gives their lengths, a second one fills windows of that size
   for (int pass = 0; pass < (found_keys ? 2 : 1); pass++) {
-    void *d_found = nullptr, *d_foff = nullptr;
+    uint8_t* d_found = nullptr;
+    uint64_t* d_foff = nullptr;
     if (pass == 1) {
-      const uint64_t* klen = reinterpret_cast<const uint64_t*>(out.data()) + n;
+      const uint64_t* klen = f_klen.in(out.data());
       for (size_t i = 0; i < n; i++) foff[i + 1] = foff[i] + klen[i];
-      e = ss->scratch(5, foff[n] ? foff[n] : 1, &d_found);
-      if (e == hipSuccess) e = ss->scratch(6, (n + 1) * sizeof(uint64_t), &d_foff);
-      if (e == hipSuccess) e = ss->upload(d_foff, foff.data(), (n + 1) * sizeof(uint64_t));
-      if (e != hipSuccess) return hip_status(e, "staging");
+      d_found = st.buf<uint8_t>(5, foff[n]);
+      d_foff = st.buf<uint64_t>(6, n + 1);
+      st.put(d_foff, foff.data(), n + 1);
+      if (!st.ok()) return st.status("staging");
     }
-    if (lsbm_block_seek_dev(static_cast<const uint8_t*>(d_image), image_size, static_cast<const uint64_t*>(d_handles),
-                            d_targets, static_cast<const uint64_t*>(d_toff), n, (int)cmp, flags, d_state, d_pos,
-                            d_klen, d_value, d_hout, static_cast<uint8_t*>(d_found),
-                            static_cast<const uint64_t*>(d_foff), foff[n], ss->stream()) != LSBM_OK)
+    if (lsbm_block_seek_dev(d.image, image_size, d.handles, d_targets, d_toff, n, (int)cmp, flags, f_state.in(d_out),
+                            f_pos.in(d_out), f_klen.in(d_out), f_value.in(d_out), f_handle.in(d_out), d_found, d_foff,
+                            foff[n], st.stream()) != LSBM_OK)
       return Status::IOError(lsbm_crc32c_last_error());
-    e = ss->download(out.data(), d_out, out_bytes);
-    if (e == hipSuccess && pass == 1 && foff[n]) {
+    st.get(out.data(), d_out, res.bytes());
+    if (pass == 1) {
       found.assign(foff[n], '\0');
-      e = ss->download(&found[0], d_found, foff[n]);
+      st.get(&found[0], d_found, foff[n]);
     }
-    if (e != hipSuccess) return hip_status(e, "block seek");
+    if (!st.ok()) return st.status("block seek");
   }
-  const uint64_t* o = reinterpret_cast<const uint64_t*>(out.data());
-  const uint32_t* st = reinterpret_cast<const uint32_t*>(o + 6 * n);
+  const uint64_t *pos = f_pos.in(out.data()), *klen = f_klen.in(out.data());
+  const uint64_t *val = f_value.in(out.data()), *hnd = f_handle.in(out.data());
+  const uint32_t* state = f_state.in(out.data());
   results->resize(n);
   Status first = Status::OK();
   for (size_t i = 0; i < n; i++) {
-    (*results)[i] = SeekResult{st[i], o[i], o[n + i], o[2 * n + 2 * i], o[2 * n + 2 * i + 1],
-                               o[4 * n + 2 * i], o[4 * n + 2 * i + 1]};
-    if (first.ok()) first = seek_status(st[i]);
+    (*results)[i] = SeekResult{state[i], pos[i], klen[i], val[2 * i], val[2 * i + 1], hnd[2 * i], hnd[2 * i + 1]};
+    if (first.ok()) first = seek_status(state[i]);
   }
   if (found_keys) {
     found_keys->resize(n);

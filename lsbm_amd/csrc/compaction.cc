@@ -10,7 +10,7 @@
 
 #include "../../include/lsbm_crc32c.h"
 #include "../../include/lsbm_merge.h"
-#include "host_session.h"
+#include "host_staging.h"
 
 namespace lsbm {
 
@@ -62,60 +62,54 @@ Status MergeRuns(int device, const BlockEntries& en, const uint64_t* run_first, 
   if (n_runs > LSBM_MERGE_MAX_RUNS) return Status::InvalidArgument("more than 64 runs");
   if (opt.cmp != kBytewiseComparator && opt.cmp != kInternalKeyComparator) return Status::InvalidArgument("unknown comparator");
   if (opt.drop && opt.cmp != kInternalKeyComparator) return Status::InvalidArgument("the drop rule needs internal keys");
-  SessionLease ss;
-  Status s = ss.Open(device);
+  Staging st;
+  Status s = st.Open(device);
   if (!s.ok()) return s;
   const size_t n = en.n;
-  const size_t off_bytes = (n + 1) * sizeof(uint64_t), val_bytes = 2 * n * sizeof(uint64_t);
-  const size_t run_bytes = (n_runs + 1) * sizeof(uint64_t);
   const uint64_t scratch_bytes = lsbm_merge_scratch_bytes(n, n_runs);
   // scratch 0: keys | 1: key_offsets values run_first | 2: plan's scratch
   // 3: source[n] plan_offsets[n+1] counts[2] out_offsets[n+1] out_values[2n] (u64) run_status[R] status (u32)
   // 4: out keys
-  const size_t res_words = 5 * n + 4;
-  const size_t res_bytes = res_words * sizeof(uint64_t) + (n_runs + 1) * sizeof(uint32_t);
-  void *d_k, *d_o, *d_s, *d_r, *d_ok;
-  hipError_t e = ss->scratch(0, en.keys_size ? en.keys_size : 1, &d_k);
-  if (e == hipSuccess) e = ss->scratch(1, off_bytes + val_bytes + run_bytes, &d_o);
-  if (e == hipSuccess) e = ss->scratch(2, scratch_bytes, &d_s);
-  if (e == hipSuccess) e = ss->scratch(3, res_bytes, &d_r);
-  if (e == hipSuccess) e = ss->scratch(4, en.keys_size ? en.keys_size : 1, &d_ok);
-  if (e == hipSuccess && en.keys_size) e = ss->upload(d_k, en.keys, en.keys_size);
-  if (e == hipSuccess) e = ss->upload(d_o, en.key_offsets, off_bytes);
-  uint64_t* d_koff = static_cast<uint64_t*>(d_o);
-  uint64_t *d_vals = d_koff + n + 1, *d_runs = d_vals + 2 * n;
-  if (e == hipSuccess && n) e = ss->upload(d_vals, en.values, val_bytes);
-  if (e == hipSuccess) e = ss->upload(d_runs, run_first, run_bytes);
-  if (e != hipSuccess) return hip_status(e, "staging");
-  uint64_t* d_source = static_cast<uint64_t*>(d_r);
-  uint64_t *d_poff = d_source + n, *d_counts = d_poff + n + 1, *d_ooff = d_counts + 2, *d_ovals = d_ooff + n + 1;
-  uint32_t* d_rst = reinterpret_cast<uint32_t*>(d_ovals + 2 * n);
-  uint32_t* d_gst = d_rst + n_runs;
+  Packed in, res;
+  const auto f_koff = in.add<uint64_t>(n + 1), f_vals = in.add<uint64_t>(2 * n), f_runs = in.add<uint64_t>(n_runs + 1);
+  const auto f_source = res.add<uint64_t>(n), f_poff = res.add<uint64_t>(n + 1), f_counts = res.add<uint64_t>(2);
+  const auto f_ooff = res.add<uint64_t>(n + 1), f_ovals = res.add<uint64_t>(2 * n);
+  const auto f_rst = res.add<uint32_t>(n_runs), f_gst = res.add<uint32_t>(1);
+  uint8_t* d_k = st.buf<uint8_t>(0, en.keys_size);
+  uint8_t* d_o = st.buf<uint8_t>(1, in.bytes());
+  uint8_t* d_s = st.buf<uint8_t>(2, scratch_bytes);
+  uint8_t* d_r = st.buf<uint8_t>(3, res.bytes());
+  uint8_t* d_ok = st.buf<uint8_t>(4, en.keys_size);
+  st.put(d_k, en.keys, en.keys_size);
+  st.put(f_koff.in(d_o), en.key_offsets, n + 1);
+  st.put(f_vals.in(d_o), en.values, 2 * n);
+  st.put(f_runs.in(d_o), run_first, n_runs + 1);
+  if (!st.ok()) return st.status("staging");
   const uint32_t flags = (opt.drop ? LSBM_MERGE_DROP : 0u) | (opt.bottom_level ? LSBM_MERGE_BOTTOM_LEVEL : 0u);
-  if (lsbm_merge_plan_dev(static_cast<uint8_t*>(d_k), en.keys_size, d_koff, n, d_runs, n_runs, (int)opt.cmp, flags,
-                          opt.smallest_snapshot, d_source, d_poff, d_counts, d_rst, d_s, scratch_bytes,
-                          ss->stream()) != LSBM_OK ||
-      lsbm_merge_gather_dev(static_cast<uint8_t*>(d_k), en.keys_size, d_koff, d_vals, n, d_source, d_poff, d_counts,
-                            static_cast<uint8_t*>(d_ok), en.keys_size, d_ooff, d_ovals, n, d_gst,
-                            ss->stream()) != LSBM_OK)
+  if (lsbm_merge_plan_dev(d_k, en.keys_size, f_koff.in(d_o), n, f_runs.in(d_o), n_runs, (int)opt.cmp, flags,
+                          opt.smallest_snapshot, f_source.in(d_r), f_poff.in(d_r), f_counts.in(d_r), f_rst.in(d_r), d_s,
+                          scratch_bytes, st.stream()) != LSBM_OK ||
+      lsbm_merge_gather_dev(d_k, en.keys_size, f_koff.in(d_o), f_vals.in(d_o), n, f_source.in(d_r), f_poff.in(d_r),
+                            f_counts.in(d_r), d_ok, en.keys_size, f_ooff.in(d_r), f_ovals.in(d_r), n, f_gst.in(d_r),
+                            st.stream()) != LSBM_OK)
     return Status::InvalidArgument(lsbm_crc32c_last_error());
-  std::vector<uint8_t> res(res_bytes);
-  e = ss->download(res.data(), d_r, res_bytes);
-  if (e != hipSuccess) return hip_status(e, "merge");
-  const uint64_t* w = reinterpret_cast<const uint64_t*>(res.data());
-  const uint32_t* st = reinterpret_cast<const uint32_t*>(w + res_words);
-  run_statuses->assign(st, st + n_runs);
+  std::vector<uint8_t> host(res.bytes());
+  st.get(host.data(), d_r, res.bytes());
+  if (!st.ok()) return st.status("merge");
+  const uint8_t* h = host.data();
+  const uint32_t* rst = f_rst.in(h);
+  run_statuses->assign(rst, rst + n_runs);
   for (size_t r = 0; r < n_runs; r++)
-    if (st[r] != LSBM_MERGE_OK) return merge_status(st[r], r);
-  if (st[n_runs] != LSBM_MERGE_OK) return Status::IOError("internal error: merge gather failed");
-  const uint64_t n_out = w[2 * n + 1], key_bytes = w[2 * n + 2];
+    if (rst[r] != LSBM_MERGE_OK) return merge_status(rst[r], r);
+  if (*f_gst.in(h) != LSBM_MERGE_OK) return Status::IOError("internal error: merge gather failed");
+  const uint64_t n_out = f_counts.in(h)[0], key_bytes = f_counts.in(h)[1];
   if (n_out > n || key_bytes > en.keys_size) return Status::IOError("internal error: merge output larger than its input");
-  source->assign(w, w + n_out);
-  key_offsets->assign(w + 2 * n + 3, w + 2 * n + 3 + n_out + 1);
-  values->assign(w + 3 * n + 4, w + 3 * n + 4 + 2 * n_out);
+  source->assign(f_source.in(h), f_source.in(h) + n_out);
+  key_offsets->assign(f_ooff.in(h), f_ooff.in(h) + n_out + 1);
+  values->assign(f_ovals.in(h), f_ovals.in(h) + 2 * n_out);
   keys->assign(key_bytes, '\0');
-  if (key_bytes) e = ss->download(&(*keys)[0], d_ok, key_bytes);
-  if (e != hipSuccess) return hip_status(e, "merge");
+  st.get(&(*keys)[0], d_ok, key_bytes);
+  if (!st.ok()) return st.status("merge");
   return Status::OK();
 }
 

@@ -14,7 +14,7 @@
 #include <memory>
 
 #include "../../include/lsbm_bloom.h"
-#include "host_session.h"
+#include "host_staging.h"
 
 namespace lsbm {
 
@@ -121,31 +121,28 @@ Status FinishFilterBlocks(int device, FilterBlockBuilder* const* builders, size_
   const size_t nf = out_off.size();
   lap(HostTiming::kPrep);
   if (nf) {  // one launch on the device's session (host_session.h)
-    SessionLease ss;
-    Status s = ss.Open(device);
+    Staging st;
+    Status s = st.Open(device);
     if (!s.ok()) return s;
-    void *d_keys, *d_offs, *d_first, *d_out_off, *d_out;
-    hipError_t e = ss->scratch(0, total_bytes ? total_bytes : 1, &d_keys);
-    if (e == hipSuccess) e = ss->scratch(1, (total_keys + 1) * sizeof(uint64_t), &d_offs);
-    if (e == hipSuccess) e = ss->scratch(2, first.size() * sizeof(uint64_t), &d_first);
-    if (e == hipSuccess) e = ss->scratch(3, out_off.size() * sizeof(uint64_t), &d_out_off);
-    if (e == hipSuccess) e = ss->scratch(4, out_total, &d_out);
+    uint8_t* d_keys = st.buf<uint8_t>(0, total_bytes);
+    uint64_t* d_offs = st.buf<uint64_t>(1, total_keys + 1);
+    uint64_t* d_first = st.buf<uint64_t>(2, first.size());
+    uint64_t* d_out_off = st.buf<uint64_t>(3, out_off.size());
+    uint8_t* d_out = st.buf<uint8_t>(4, out_total);
     std::vector<HostSession::Piece> pieces(n);  // every builder's keys, back to back: one gather
     for (size_t t = 0; t < n; t++) pieces[t] = HostSession::Piece{builders[t]->keys_.data(), builders[t]->keys_.size()};
-    if (e == hipSuccess) e = ss->upload_pieces(d_keys, pieces.data(), n);
-    if (e == hipSuccess) e = ss->upload(d_offs, key_offs.get(), (total_keys + 1) * sizeof(uint64_t));
-    if (e == hipSuccess) e = ss->upload(d_first, first.data(), first.size() * sizeof(uint64_t));
-    if (e == hipSuccess) e = ss->upload(d_out_off, out_off.data(), out_off.size() * sizeof(uint64_t));
-    if (e != hipSuccess) return hip_status(e, "staging");
+    st.put_pieces(d_keys, pieces);
+    st.put(d_offs, key_offs.get(), total_keys + 1);
+    st.put(d_first, first.data(), first.size());
+    st.put(d_out_off, out_off.data(), out_off.size());
+    if (!st.ok()) return st.status("staging");
     lap(HostTiming::kCopy);
-    if (lsbm_bloom_build_dev(static_cast<const uint8_t*>(d_keys), static_cast<const uint64_t*>(d_offs),
-                             internal ? LSBM_INTERNAL_KEY_SUFFIX : 0,
-                             static_cast<const uint64_t*>(d_first), static_cast<const uint64_t*>(d_out_off),
-                             nf, bpk, static_cast<uint8_t*>(d_out), ss->stream()) != LSBM_OK)
+    if (lsbm_bloom_build_dev(d_keys, d_offs, internal ? LSBM_INTERNAL_KEY_SUFFIX : 0, d_first, d_out_off, nf, bpk,
+                             d_out, st.stream()) != LSBM_OK)
       return Status::IOError(lsbm_crc32c_last_error());
     lap(HostTiming::kEnqueue);
-    e = ss->download(data.get(), d_out, out_total);
-    if (e != hipSuccess) return hip_status(e, "filters");
+    st.get(data.get(), d_out, out_total);
+    if (!st.ok()) return st.status("filters");
     lap(HostTiming::kWait);
   }
   for (size_t t = 0; t < n; t++) {  // :41-49
@@ -169,39 +166,34 @@ Status FilterBlockReader::KeyMayMatch(int device, const uint64_t* block_offsets,
   may->assign(n, 1);
   if (n == 0) return Status::OK();
   if (!block_offsets || !keys || !key_offsets) return Status::InvalidArgument("null pointer");
-  SessionLease ss;
-  Status s = ss.Open(device);
+  Staging st;
+  Status s = st.Open(device);
   if (!s.ok()) return s;
-  std::vector<uint64_t> handles(2 * n), offs(n + 1);
+  std::vector<uint64_t> handles(2 * n);
   for (size_t i = 0; i < n; i++) {
     handles[2 * i] = 0;
     handles[2 * i + 1] = size_;
   }
-  for (size_t i = 0; i <= n; i++) offs[i] = key_offsets[i] - key_offsets[0];
-  void *d_block, *d_keys, *d_may, *d_handles, *d_data, *d_offs;
-  hipError_t e = ss->scratch(0, size_, &d_block);
-  if (e == hipSuccess) e = ss->scratch(1, handles.size() * sizeof(uint64_t), &d_handles);
-  if (e == hipSuccess) e = ss->scratch(2, n * sizeof(uint64_t), &d_data);
-  if (e == hipSuccess) e = ss->scratch(3, offs[n], &d_keys);
-  if (e == hipSuccess) e = ss->scratch(4, offs.size() * sizeof(uint64_t), &d_offs);
-  if (e == hipSuccess) e = ss->scratch(5, n, &d_may);
-  if (e == hipSuccess) e = ss->upload(d_block, contents_, size_);
-  if (e == hipSuccess) e = ss->upload(d_handles, handles.data(), handles.size() * sizeof(uint64_t));
-  if (e == hipSuccess) e = ss->upload(d_data, block_offsets, n * sizeof(uint64_t));
-  if (e == hipSuccess) e = ss->upload(d_keys, keys + key_offsets[0], offs[n]);
-  if (e == hipSuccess) e = ss->upload(d_offs, offs.data(), offs.size() * sizeof(uint64_t));
-  if (e != hipSuccess) return hip_status(e, "staging");
-  if (lsbm_filter_block_may_match_dev(static_cast<const uint8_t*>(d_block),
-                                      static_cast<const uint64_t*>(d_handles),
-                                      static_cast<const uint64_t*>(d_data),
-                                      static_cast<const uint8_t*>(d_keys),
-                                      static_cast<const uint64_t*>(d_offs),
+  const std::vector<uint64_t> offs = rebased(key_offsets, n);
+  uint8_t* d_block = st.buf<uint8_t>(0, size_);
+  uint64_t* d_handles = st.buf<uint64_t>(1, handles.size());
+  uint64_t* d_data = st.buf<uint64_t>(2, n);
+  uint8_t* d_keys = st.buf<uint8_t>(3, offs[n]);
+  uint64_t* d_offs = st.buf<uint64_t>(4, offs.size());
+  uint8_t* d_may = st.buf<uint8_t>(5, n);
+  st.put(d_block, contents_, size_);
+  st.put(d_handles, handles.data(), handles.size());
+  st.put(d_data, block_offsets, n);
+  st.put(d_keys, keys + key_offsets[0], offs[n]);
+  st.put(d_offs, offs.data(), offs.size());
+  if (!st.ok()) return st.status("staging");
+  if (lsbm_filter_block_may_match_dev(d_block, d_handles, d_data, d_keys, d_offs,
                                       options_.internal_keys ? LSBM_INTERNAL_KEY_SUFFIX : 0, n,
-                                      options_.bits_per_key, options_.bloom_bits_use,
-                                      static_cast<uint8_t*>(d_may), nullptr, ss->stream()) != LSBM_OK)
+                                      options_.bits_per_key, options_.bloom_bits_use, d_may, nullptr,
+                                      st.stream()) != LSBM_OK)
     return Status::IOError(lsbm_crc32c_last_error());
-  e = ss->download(may->data(), d_may, n);
-  return e == hipSuccess ? Status::OK() : hip_status(e, "lookups");
+  st.get(may->data(), d_may, n);
+  return st.ok() ? Status::OK() : st.status("lookups");
 }
 
 }  // namespace lsbm

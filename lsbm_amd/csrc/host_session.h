@@ -1,6 +1,9 @@
 // host_session.h -- persistent per-device staging for the C++ host layers
-// (table_checksum.cc, log_checksum.cc, filter_block.cc, block_compression.cc)
-// and the host-staged batch entry point (crc32c_engine.cc).
+// and the host-staged batch entry point (crc32c_engine.cc).  table_checksum.cc
+// and log_checksum.cc run the staged pipeline (Stage::bulk / meta / res); the
+// single-shot layers (block_reader.cc, block_builder.cc, compaction.cc,
+// memtable_flush.cc, filter_block.cc, block_compression.cc) use the scratch
+// slots through host_staging.h.
 //
 // A HostSession belongs to one device and is created on that device when a
 // layer needs one and none is idle (up to LSBM_HOST_SESSIONS, default 8, per

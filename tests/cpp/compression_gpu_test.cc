@@ -41,6 +41,23 @@ static std::string make_block(std::mt19937_64& rng, size_t n, int kind) {
 }
 
 int main() {
+  // first, on the process's new session: one snappy block whose preamble fails
+  // the length check gets a zero-size window, which is still a valid pointer
+  {
+    const std::string bad = std::string("\xff\xff\xff\xff\x0f", 5) + std::string(40, 'a');
+    const uint64_t boffs[2] = {0, bad.size()};
+    const uint8_t btype = lsbm::kSnappyCompression;
+    std::string back("x");
+    std::vector<uint64_t> boff;
+    std::vector<uint8_t> ok;
+    lsbm::Status s = lsbm::UncompressBlocks(0, bad.data(), boffs, &btype, 1, &back, &boff, &ok);
+    EXPECT(s.ToString() == "Corruption: corrupted compressed block contents");
+    if (s.ToString() != "Corruption: corrupted compressed block contents") printf("got: %s\n", s.ToString().c_str());
+    EXPECT((ok == std::vector<uint8_t>{0}));
+    EXPECT(back.empty());
+    EXPECT((boff == std::vector<uint64_t>{0, 0}));
+  }
+
   std::mt19937_64 rng(20261016);
   const size_t n = 1500;
   std::string raw;

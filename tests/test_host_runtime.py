@@ -148,6 +148,22 @@ def test_pool_under_thread_sanitizer(tmp_path):
     assert "WARNING: ThreadSanitizer" not in r.stderr, r.stderr[-3000:]
 
 
+def test_staging_layout_under_address_sanitizer(tmp_path):
+    """The packed-buffer layout the scratch-slot layers share (host_staging.h:
+    Packed, Field), built alone with -fsanitize=address,undefined: offsets and
+    totals of back-to-back fields, empty fields, typed pointers into a mutable
+    and a const base (tests/cpp/staging_layout_test.cc)."""
+    import subprocess
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "staging_layout_test"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", os.path.join(repo, "tests", "cpp", "staging_layout_test.cc"),
+                    "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    assert r.stdout.startswith("OK"), r.stdout
+
+
 def test_cgroup_quota_of_the_process_own_cgroup(product_lib, tmp_path):
     """usable_cores() reads the quota of the process's OWN cgroup (its path in
     /proc/self/cgroup), the smallest over it and its ancestors -- not the
