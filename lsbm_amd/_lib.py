@@ -161,6 +161,17 @@ ITER_SIGNATURES = {
                                     _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
 }
 
+# every symbol include/lsbm_write.h declares
+WRITE_SIGNATURES = {
+    "lsbm_write_scratch_bytes": (_u64, [_u64, _u64]),
+    "lsbm_write_sizes_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "lsbm_write_group_dev": (_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp]),
+    "lsbm_write_build_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u64, _vp,
+                                    _u64, _vp, _vp, _vp, _vp, _vp]),
+    "lsbm_log_frame_plan_dev": (_int, [_u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "lsbm_log_frame_dev": (_int, [_vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -183,7 +194,8 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(BLOCK_SIGNATURES.items())
                                   + list(BLOCK_BUILD_SIGNATURES.items()) + list(MERGE_SIGNATURES.items())
                                   + list(TABLE_PACK_SIGNATURES.items()) + list(MEMTABLE_SIGNATURES.items())
-                                  + list(GET_SIGNATURES.items()) + list(ITER_SIGNATURES.items())):
+                                  + list(GET_SIGNATURES.items()) + list(ITER_SIGNATURES.items())
+                                  + list(WRITE_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)
