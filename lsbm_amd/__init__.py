@@ -3,7 +3,8 @@
   lsbm_amd.crc32c   util/crc32c.h mirror (Value / Extend / Mask / Unmask)
   lsbm_amd.engine   device-resident and host-staged batches (GPU)
   lsbm_amd.table    SSTable block trailers: batched WriteRawBlock / ReadBlock verify
-  lsbm_amd.log      WAL / MANIFEST record CRCs: batched log::Writer seal / log::Reader check
+  lsbm_amd.log      WAL / MANIFEST record CRCs: batched log::Writer seal / log::Reader check; the batched
+                    log::Reader itself: block walk, ReadRecord with every Reporter call (read_records)
   lsbm_amd.bloom    SSTable bloom filters: batched CreateFilter / KeyMayMatch / filter blocks
   lsbm_amd.snappy   SSTable block compression: batched snappy RawCompress / RawUncompress
   lsbm_amd.block    SSTable block reader: batched Block::Iter scan / decode / Seek, Table::InternalGet
@@ -14,7 +15,8 @@
   lsbm_amd.sstable  tables with snappy-compressed blocks: WriteBlock's keep rule and block packing,
                     batched ReadBlock, table writer, Get and compaction over either block type
   lsbm_amd.memtable memtable flush: batched WriteBatch::Iterate over log records, the memtable's
-                    iteration order as a sort, log image -> Level-0 table file
+                    iteration order as a sort, log image -> Level-0 table file (recover: RecoverLogFile
+                    over a log in device memory)
   lsbm_amd.db       batched DB::Get: LookupKey, MemTable::Get, FindFile, SaveValue, and the chain over
                     memtables and table files (Version.get)
   lsbm_amd.scan     batched range scans: DBIter's snapshot view of merged entries, Seek / SeekToFirst /
@@ -25,7 +27,7 @@
 The compute lives in lsbm_amd/liblsbm_crc32c.so (hand-written gfx950 HIP
 kernels behind the C ABIs in include/lsbm_crc32c.h, include/lsbm_bloom.h, include/lsbm_snappy.h and
 include/lsbm_block.h, include/lsbm_block_build.h, include/lsbm_merge.h, include/lsbm_table_pack.h,
-include/lsbm_memtable.h, include/lsbm_get.h, include/lsbm_iter.h, include/lsbm_write.h).
+include/lsbm_memtable.h, include/lsbm_get.h, include/lsbm_iter.h, include/lsbm_write.h, include/lsbm_log_read.h).
 """
 from ._lib import LIB_PATH, LsbmError, lib  # noqa: F401
 

@@ -172,6 +172,19 @@ WRITE_SIGNATURES = {
     "lsbm_log_frame_dev": (_int, [_vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
 }
 
+# every symbol include/lsbm_log_read.h declares
+LOG_READ_SIGNATURES = {
+    "lsbm_log_read_scratch_bytes": (_u64, [_u64]),
+    "lsbm_log_read_plan_scratch_bytes": (_u64, [_u64, _u64]),
+    "lsbm_log_read_blocks": (_u64, [_u64, _u64]),
+    "lsbm_log_read_walk_dev": (_int, [_vp, _u64, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64,
+                                      _vp]),
+    "lsbm_log_read_plan_dev": (_int, [_vp, _u64, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp,
+                                      _u64, _vp]),
+    "lsbm_log_read_emit_dev": (_int, [_vp, _u64, _u64, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _u64,
+                                      _vp, _vp, _u64, _vp]),
+}
+
 _lib = None
 
 
@@ -195,7 +208,7 @@ def lib():
                                   + list(BLOCK_BUILD_SIGNATURES.items()) + list(MERGE_SIGNATURES.items())
                                   + list(TABLE_PACK_SIGNATURES.items()) + list(MEMTABLE_SIGNATURES.items())
                                   + list(GET_SIGNATURES.items()) + list(ITER_SIGNATURES.items())
-                                  + list(WRITE_SIGNATURES.items())):
+                                  + list(WRITE_SIGNATURES.items()) + list(LOG_READ_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)

@@ -21,6 +21,9 @@ torch's current stream).
                                        {offset, length} pairs, fragments
                                        assembled on the device
     recover_log(image_host, ...)       log_records, then flush
+    recover(image, ...)                log.read_records, then flush: a log in
+                                       device memory, torn tail and corruption
+                                       reports included (RecoverLogFile)
 
 A record is image[records[2i], records[2i] + records[2i+1]): one
 WriteBatch::rep_ (int64 {offset, length} pairs).  Entries are what block.decode
@@ -56,6 +59,7 @@ STATUS_MESSAGE = {WB_TOO_SMALL: "log record too small", WB_BAD_PUT: "bad WriteBa
 DecodeResult = namedtuple("DecodeResult", "keys key_offsets values max_sequence status")
 EntriesResult = namedtuple("EntriesResult", "keys key_offsets values status max_sequence")
 FlushResult = namedtuple("FlushResult", "image data_handles index_handle smallest largest max_sequence status")
+RecoverResult = namedtuple("RecoverResult", "flush events status")
 
 
 def _check(**ts):
@@ -308,3 +312,35 @@ def recover_log(image_host, compression=kNoCompression, block_size=4096, restart
     """RecoverLogFile for a log that fits one memtable: log_records, then flush."""
     image, records = log_records(image_host, device, stream)
     return flush(image, records, compression, block_size, restart_interval, bits_per_key, paranoid, stream)
+
+
+def recover(image, paranoid=False, compression=kNoCompression, block_size=4096, restart_interval=16,
+            bits_per_key=None, stream=None, log_bytes=None):
+    """DBImpl::RecoverLogFile (lsbm/db_impl.cc:398-470) for a log that lies in
+    device memory (the first log_bytes bytes of `image`) and fits one memtable:
+    log.read_records, then flush.  RecoverResult(flush, events, status): flush
+    is the FlushResult of the records inserted, events the reader's
+    Reporter::Corruption calls (int64[m, 4], log.REASONS), status None or the
+    status RecoverLogFile returns.
+
+    paranoid=False: every report is ignored (the reporter only logs); records
+    shorter than 12 bytes are dropped as "log record too small", which is
+    flush's WB_TOO_SMALL.  paranoid=True: the first report sets the status and
+    ends the loop, which tests it after ReadRecord returns: the records
+    returned before the reporting call are inserted, the one that call returned
+    is not; a record that WriteBatch::Iterate rejects raises ValueError with the
+    reference's message, as flush(paranoid=True) does."""
+    torch = _torch()
+    from . import log
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return recover(image, paranoid, compression, block_size, restart_interval, bits_per_key, None, log_bytes)
+    r = log.read_records(image, log_bytes)
+    records, status = r.records, None
+    if paranoid and r.events.shape[0]:
+        before, _, reason, arg = r.events[0].cpu().tolist()
+        records = records[:before]
+        status = "Corruption: " + log.REASONS[reason] + (f" {arg & 0xFFFFFFFF}" if reason == 10 else "")
+    f = flush(r.image, records.reshape(-1).contiguous(), compression, block_size, restart_interval, bits_per_key,
+              paranoid)
+    return RecoverResult(f, r.events, status)
