@@ -185,6 +185,15 @@ LOG_READ_SIGNATURES = {
                                       _vp, _vp, _u64, _vp]),
 }
 
+# every symbol include/lsbm_memtable_cut.h declares
+MEMCUT_SIGNATURES = {
+    "lsbm_skiplist_heights_scratch_bytes": (_u64, [_u64]),
+    "lsbm_memtable_cut_scratch_bytes": (_u64, [_u64, _u64]),
+    "lsbm_skiplist_heights_dev": (_int, [_u64, _u64, _vp, _vp, _vp, _u64, _vp]),
+    "lsbm_memtable_cut_dev": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _u32, _u64, _vp, _vp, _vp, _vp, _u64,
+                                     _vp, _vp, _vp, _vp, _u64, _vp]),
+}
+
 _lib = None
 
 
@@ -208,7 +217,8 @@ def lib():
                                   + list(BLOCK_BUILD_SIGNATURES.items()) + list(MERGE_SIGNATURES.items())
                                   + list(TABLE_PACK_SIGNATURES.items()) + list(MEMTABLE_SIGNATURES.items())
                                   + list(GET_SIGNATURES.items()) + list(ITER_SIGNATURES.items())
-                                  + list(WRITE_SIGNATURES.items()) + list(LOG_READ_SIGNATURES.items())):
+                                  + list(WRITE_SIGNATURES.items()) + list(LOG_READ_SIGNATURES.items())
+                                  + list(MEMCUT_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)

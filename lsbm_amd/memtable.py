@@ -24,18 +24,26 @@ torch's current stream).
     recover(image, ...)                log.read_records, then flush: a log in
                                        device memory, torn tail and corruption
                                        reports included (RecoverLogFile)
+    heights(n, rnd)                    SkipList::RandomHeight of n inserts
+    cut(key_offsets, values, ...)      ApproximateMemoryUsage() after every
+                                       record and where RecoverLogFile or
+                                       MakeRoomForWrite ends a memtable
+                                       (include/lsbm_memtable_cut.h)
+    recover_all(image, ...)            recover for a log of any size: one
+                                       Level-0 table per memtable
 
 A record is image[records[2i], records[2i] + records[2i+1]): one
 WriteBatch::rep_ (int64 {offset, length} pairs).  Entries are what block.decode
 returns and block_build, bloom, merge and sstable.write_table read.  One call
-is one memtable: the caller chooses which records go in.
+of scan .. recover is one memtable; cut says which records go into which,
+and recover_all flushes each.
 """
 from collections import namedtuple
 
 import numpy as np
 
 from ._lib import check, lib
-from .engine import _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _buf, _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
 from .log import kBlockSize, kFirstType, kFullType, kHeaderSize, kLastType, kMiddleType
 from .merge import MERGE_OK, PlanResult
 from .table import kNoCompression
@@ -60,6 +68,14 @@ DecodeResult = namedtuple("DecodeResult", "keys key_offsets values max_sequence 
 EntriesResult = namedtuple("EntriesResult", "keys key_offsets values status max_sequence")
 FlushResult = namedtuple("FlushResult", "image data_handles index_handle smallest largest max_sequence status")
 RecoverResult = namedtuple("RecoverResult", "flush events status")
+CutResult = namedtuple("CutResult", "usage mem_first mem_usage counts state status")
+RecoverAllResult = namedtuple("RecoverAllResult", "flushes mem_first events status")
+
+# include/lsbm_memtable_cut.h
+RECOVER, WRITE = 0, 1
+SKIPLIST_SEED = 0xdeadbeef & 0x7fffffff
+FRESH_USAGE = 4104
+kMinWriteBuffer, kMaxWriteBuffer = 64 << 10, 1 << 30  # SanitizeOptions, lsbm/db_impl.cc
 
 
 def _check(**ts):
@@ -344,3 +360,138 @@ def recover(image, paranoid=False, compression=kNoCompression, block_size=4096, 
     f = flush(r.image, records.reshape(-1).contiguous(), compression, block_size, restart_interval, bits_per_key,
               paranoid)
     return RecoverResult(f, r.events, status)
+
+
+def heights(n, rnd=SKIPLIST_SEED, stream=None, device="cuda"):
+    """(heights uint8[n], rnd_out int64[1]): SkipList::RandomHeight of n
+    consecutive inserts from generator state rnd (a new memtable's by default),
+    and the state after them."""
+    torch = _torch()
+    out = torch.zeros(max(n, 1), dtype=torch.uint8, device=device)[:n]
+    rnd_out = torch.zeros(1, dtype=torch.int64, device=device)
+    nbytes = lib().lsbm_skiplist_heights_scratch_bytes(n)
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    check(lib().lsbm_skiplist_heights_dev(rnd, n, _ptr(out), _ptr(rnd_out), _ptr(scratch), scratch.numel() * 8,
+                                          _stream_ptr(stream)), "lsbm_skiplist_heights_dev")
+    return out, rnd_out
+
+
+def clip_write_buffer(write_buffer_size):
+    """SanitizeOptions' clip of write_buffer_size to [64 KiB, 1 GiB]."""
+    return min(max(int(write_buffer_size), kMinWriteBuffer), kMaxWriteBuffer)
+
+
+def cut(key_offsets, values, entry_base, mode, write_buffer_size, key_extra=0, types=None, rec_status=None,
+        state=None, mem_cap=None, usage=None, mem_first=None, mem_usage=None, counts=None, state_out=None,
+        status=None, stream=None):
+    """CutResult(usage int64[n_records], mem_first int64[mem_cap + 1], mem_usage
+    int64[mem_cap], counts int64[2] = {memtables, the first is the state's},
+    state int64[6], status int32[1]) of lsbm_memtable_cut_dev.  key_offsets and
+    values are decode's (key_extra 0) or write.sizes' inputs (key_extra 8, with
+    `types`); `state` is a prior call's.  write_buffer_size is taken as given
+    (clip_write_buffer is SanitizeOptions').  Without mem_cap every record may
+    begin a memtable."""
+    torch = _torch()
+    _require_cuda(key_offsets, values, entry_base, types, rec_status, state, usage, mem_first, mem_usage, counts,
+                  state_out, status)
+    _check_tensors(dict(key_offsets=key_offsets, values=values, entry_base=entry_base, types=types,
+                        rec_status=rec_status, state=state, usage=usage, mem_first=mem_first, mem_usage=mem_usage,
+                        counts=counts, state_out=state_out, status=status), u8=("types",),
+                   i32=("rec_status", "status"))
+    n, nr, dev = key_offsets.numel() - 1, entry_base.numel() - 1, key_offsets.device
+    if n < 0 or nr < 0 or values.numel() != 2 * n or (types is not None and types.numel() != n) or \
+            (rec_status is not None and rec_status.numel() != nr) or (state is not None and state.numel() != 6):
+        raise ValueError("key_offsets[n + 1], values[2n], types[n], entry_base[n_records + 1], rec_status[n_records] "
+                         "and state[6] are needed")
+    if mem_cap is None:
+        mem_cap = nr + 1 if mem_first is None else mem_first.numel() - 1
+    if usage is None:
+        usage = _buf(nr, torch.int64, dev)
+    if mem_first is None:
+        mem_first = _buf(mem_cap + 1, torch.int64, dev)
+    if mem_usage is None:
+        mem_usage = _buf(mem_cap, torch.int64, dev)
+    if counts is None:
+        counts = _buf(2, torch.int64, dev)
+    if state_out is None:
+        state_out = _buf(6, torch.int64, dev)
+    if status is None:
+        status = _buf(1, torch.int32, dev)
+    if usage.numel() != nr or mem_first.numel() < mem_cap + 1 or mem_usage.numel() < mem_cap or \
+            counts.numel() != 2 or state_out.numel() != 6 or status.numel() != 1:
+        raise ValueError("usage[n_records], mem_first[mem_cap + 1], mem_usage[mem_cap], counts[2], state_out[6] and "
+                         "status[1] are needed")
+    nbytes = lib().lsbm_memtable_cut_scratch_bytes(n, nr)
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    check(lib().lsbm_memtable_cut_dev(_ptr(key_offsets), n, key_extra, _ptr(values), _ptr(types), _ptr(entry_base), nr,
+                                      _ptr(rec_status), mode, write_buffer_size, _ptr(state), _ptr(usage),
+                                      _ptr(mem_first), _ptr(mem_usage), mem_cap, _ptr(counts), _ptr(state_out),
+                                      _ptr(status), _ptr(scratch), scratch.numel() * 8, _stream_ptr(stream)),
+          "lsbm_memtable_cut_dev")
+    return CutResult(usage, mem_first, mem_usage, counts, state_out, status)
+
+
+def recover_all(image, write_buffer_size=4 << 20, paranoid=False, compression=kNoCompression, block_size=4096,
+                restart_interval=16, bits_per_key=None, stream=None, log_bytes=None):
+    """DBImpl::RecoverLogFile (lsbm/db_impl.cc:398-479) for a log of any size in
+    device memory: log.read_records, scan, decode, cut in RECOVER mode, then
+    one flush per memtable.  RecoverAllResult(flushes, mem_first, events,
+    status): flushes are the FlushResults in file order (a memtable without an
+    entry writes no table and has none), mem_first the first record of every
+    memtable closed by the count of the records the loop took (a list), events
+    and status as recover gives them.  write_buffer_size is clipped as SanitizeOptions clips it.
+
+    paranoid=True: the loop ends at the reader's first report or at the first
+    record WriteBatch::Iterate rejects (status: the reference's message); the
+    tables of the memtables that ended before it are written, the memtable in
+    progress is not (RecoverLogFile returns before its WriteLevel0Table)."""
+    torch = _torch()
+    from . import log
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return recover_all(image, write_buffer_size, paranoid, compression, block_size, restart_interval,
+                               bits_per_key, None, log_bytes)
+    r = log.read_records(image, log_bytes)
+    records, status = r.records, None
+    if paranoid and r.events.shape[0]:
+        before, _, reason, arg = r.events[0].cpu().tolist()
+        records = records[:before]
+        status = "Corruption: " + log.REASONS[reason] + (f" {arg & 0xFFFFFFFF}" if reason == 10 else "")
+    records = records.reshape(-1).contiguous()
+    n = _n_records(records)
+    counts, scan_status = scan(r.image, records)
+    if paranoid and n:
+        # the first record WriteBatch::Iterate rejects ends the loop: found on the device, one read; the records
+        # from it on are neither decoded nor counted
+        bad = scan_status != WB_OK
+        first = bad.to(torch.int64).argmax()
+        any_bad, first, st = torch.stack([bad.any().to(torch.int64), first,
+                                          scan_status[first].to(torch.int64)]).cpu().tolist()
+        if any_bad:
+            if st in (WB_BAD_INPUT, WB_NO_ROOM):
+                raise ValueError(f"record {first}: {STATUS_MESSAGE.get(st, st)}")
+            records, counts, n = records[:2 * first].contiguous(), counts[:first], first
+            status = "Corruption: " + STATUS_MESSAGE[st]
+    entry_base, key_base = bases(counts)
+    d = decode(r.image, records, entry_base, key_base)
+    c = cut(d.key_offsets, d.values.reshape(-1), entry_base, RECOVER, clip_write_buffer(write_buffer_size),
+            rec_status=d.status)
+    fatal = (d.status == WB_BAD_INPUT) | (d.status == WB_NO_ROOM)
+    n_mem, cut_st, n_fatal, open_last = torch.stack([c.counts[0], c.status[0].to(torch.int64), fatal.sum(),
+                                                     c.state[0]]).cpu().tolist()
+    if n_fatal:
+        i = int(fatal.to(torch.int64).argmax().cpu())
+        raise ValueError(f"record {i}: {STATUS_MESSAGE.get(int(d.status[i].cpu()), '')}")
+    if cut_st != MERGE_OK:
+        raise ValueError(f"internal error: cut status {cut_st}")
+    mem_first = c.mem_first[:n_mem + 1].cpu().tolist()
+    flushes = []
+    for m in range(n_mem):
+        lo, hi = mem_first[m], mem_first[m + 1]
+        if status is not None and m == n_mem - 1 and open_last:
+            break  # the loop ended early: the memtable in progress is not written
+        f = flush(r.image, records[2 * lo:2 * hi].contiguous(), compression, block_size, restart_interval,
+                  bits_per_key, False)
+        if f.image is not None:
+            flushes.append(f)
+    return RecoverAllResult(flushes, mem_first, r.events, status)

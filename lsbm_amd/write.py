@@ -18,6 +18,8 @@ out; every call enqueues on `stream` (default: torch's current stream).
     write_batches(...)               the chain, sealed: WriteResult
     frame_records(image, records)    frame_plan + frame + seal for any records
                                      (MANIFEST records too)
+    write_logs(...)                  write_batches with MakeRoomForWrite's switch:
+                                     a new log wherever the memtable is full
 
 A call models `n_writers` writers already queued in `writers_` in the given
 order, each with a non-NULL batch: ops are `types` (uint8: 1 Put, 0 Delete),
@@ -25,9 +27,11 @@ user keys `keys` + `key_offsets`, values as int64 {offset, length} pairs into
 `value_image`, and `batch_first[n_writers + 1]` the op range of each writer's
 batch.  `memtable.entries(result.reps, result.records)` reads the reps as they
 are.  Every call has one status word (MERGE_OK / MERGE_NO_ROOM / MERGE_BAD_INPUT
-of include/lsbm_block_build.h); on an error no other output changes.  Out of
-scope: MakeRoomForWrite (the caller chooses which writers go into this log),
-NULL batches, logfile_->Sync() itself (group_sync says where it falls).
+of include/lsbm_block_build.h); on an error no other output changes.
+write_batches appends every group to one log; write_logs switches logs where
+MakeRoomForWrite does (memtable.cut in WRITE mode; imm_, background errors and
+the Level-0 stall stay with the caller).  Out of scope: NULL batches,
+logfile_->Sync() itself (group_sync says where it falls).
 """
 from collections import namedtuple
 
@@ -47,6 +51,9 @@ FrameResult = namedtuple("FrameResult", "out headers status")
 WriteResult = namedtuple("WriteResult", "log headers reps records group_first group_sync sequences counts "
                                         "last_sequence end_offset")
 FramedRecords = namedtuple("FramedRecords", "log headers end_offset")
+LogSegment = namedtuple("LogSegment", "log headers records first_group n_groups end_offset")
+WriteLogsResult = namedtuple("WriteLogsResult", "logs first_log_continues reps records group_first group_sync "
+                                                "sequences counts mem_first usage mem_state last_sequence")
 
 
 def _check(**ts):
@@ -277,5 +284,59 @@ def write_batches(types, keys, key_offsets, value_image, values, batch_first, sy
                        b.seq_counts[:, 0], b.seq_counts[:, 1], last_sequence + (key_offsets.numel() - 1), end)
 
 
-__all__ = ["sizes", "group", "build", "frame_plan", "frame", "frame_records", "write_batches", "WriteResult",
+def write_logs(types, keys, key_offsets, value_image, values, batch_first, sync=None, last_sequence=0,
+               write_buffer_size=4 << 20, mem_state=None, log_offset=0, stream=None):
+    """DBImpl::Write of every queued writer with MakeRoomForWrite's switch
+    (lsbm/db_impl.cc:1469-1505, with imm_ == NULL, no background error and no
+    Level-0 stall): sizes -> group -> memtable.cut(WRITE) over the groups ->
+    build -> frame_records per log.  Before a group whose memtable reports more
+    than write_buffer_size (clipped as SanitizeOptions clips it) a new log and
+    a new memtable begin.  WriteLogsResult(logs, first_log_continues, reps,
+    records, group_first, group_sync, sequences, counts, mem_first, usage,
+    mem_state, last_sequence): logs are LogSegments in order, each the bytes
+    appended to one log file, its physical records, its groups' {offset,
+    length} records into `reps`, and its end offset; the first continues the
+    current log at log_offset when first_log_continues, every other one is a
+    new file from offset 0.  mem_state (int64[6], None for a new memtable) is
+    the memtable's accounting; pass the returned one to the next call."""
+    torch = _torch()
+    from . import memtable as _mt
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return write_logs(types, keys, key_offsets, value_image, values, batch_first, sync, last_sequence,
+                              write_buffer_size, mem_state, log_offset)
+    dev = key_offsets.device
+    s = sizes(types, key_offsets, keys.numel(), values, value_image.numel(), batch_first)
+    g = group(batch_sum=s.batch_sum, sync=sync)
+    st_s, st_g, n_groups, body = torch.stack([s.status[0].to(torch.int64), g.status[0].to(torch.int64), g.n_groups[0],
+                                              s.op_sum[-1]]).cpu().tolist()
+    _raise(st_s, "sizes")
+    _raise(st_g, "group")
+    group_first = g.group_first[:n_groups + 1].contiguous()
+    entry_base = batch_first[group_first].contiguous()  # the ops of each group
+    c = _mt.cut(key_offsets, values, entry_base, _mt.WRITE, _mt.clip_write_buffer(write_buffer_size), key_extra=8,
+                types=types, state=mem_state)
+    reps = _buf(kBatchHeader * n_groups + body, torch.uint8, dev)
+    b = build(types, keys, key_offsets, value_image, values, batch_first, s.op_sum, g.group_first, n_groups,
+              last_sequence, reps)
+    had_mem = torch.zeros(1, dtype=torch.int64, device=dev) if mem_state is None else mem_state[:1]
+    st_b, st_c, n_mem, continues, had = torch.stack([b.status[0].to(torch.int64), c.status[0].to(torch.int64),
+                                                     c.counts[0], c.counts[1], had_mem[0]]).cpu().tolist()
+    _raise(st_b, "build")
+    _raise(st_c, "cut")
+    mem_first = c.mem_first[:n_mem + 1].cpu().tolist()
+    first_continues = bool(continues) or not had  # (without a memtable the caller's log is the new, empty one)
+    logs = []
+    for m in range(n_mem):
+        lo, hi = mem_first[m], mem_first[m + 1]
+        recs = b.records[2 * lo:2 * hi].contiguous()
+        f = frame_records(reps, recs, log_offset if m == 0 and first_continues else 0)
+        logs.append(LogSegment(f.log, f.headers, recs, lo, hi - lo, f.end_offset))
+    return WriteLogsResult(logs, first_continues, reps, b.records, group_first, g.group_sync[:n_groups],
+                           b.seq_counts[:, 0], b.seq_counts[:, 1], mem_first, c.usage, c.state,
+                           last_sequence + (key_offsets.numel() - 1))
+
+
+__all__ = ["sizes", "group", "build", "frame_plan", "frame", "frame_records", "write_batches", "write_logs", "WriteResult",
+           "WriteLogsResult", "LogSegment",
            "OK", "NO_ROOM", "BAD_INPUT", "kBlockSize", "kHeaderSize", "kBatchHeader"]
