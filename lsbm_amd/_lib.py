@@ -194,6 +194,19 @@ MEMCUT_SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _u64, _vp]),
 }
 
+# every symbol include/lsbm_table_write.h declares
+TABLE_WRITE_SIGNATURES = {
+    "lsbm_table_write_scratch_bytes": (_u64, [_u64, _u64]),
+    "lsbm_table_pack_plan_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "lsbm_filter_layout_dev": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp,
+                                      _vp, _vp, _u64, _vp]),
+    "lsbm_metaindex_build_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "lsbm_table_place_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp,
+                                    _u64, _vp]),
+    "lsbm_memtable_sort_segments_scratch_bytes": (_u64, [_u64, _u64]),
+    "lsbm_memtable_sort_segments_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+}
+
 _lib = None
 
 
@@ -218,7 +231,7 @@ def lib():
                                   + list(TABLE_PACK_SIGNATURES.items()) + list(MEMTABLE_SIGNATURES.items())
                                   + list(GET_SIGNATURES.items()) + list(ITER_SIGNATURES.items())
                                   + list(WRITE_SIGNATURES.items()) + list(LOG_READ_SIGNATURES.items())
-                                  + list(MEMCUT_SIGNATURES.items())):
+                                  + list(MEMCUT_SIGNATURES.items()) + list(TABLE_WRITE_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)

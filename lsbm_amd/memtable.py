@@ -31,6 +31,14 @@ torch's current stream).
                                        (include/lsbm_memtable_cut.h)
     recover_all(image, ...)            recover for a log of any size: one
                                        Level-0 table per memtable
+    sort_segments(keys, key_offsets, seg_first)
+                                       sort over the memtables of one log, kept
+                                       apart (include/lsbm_table_write.h)
+    flush_many(image, records, mem_first, ...)
+                                       flush of every memtable of a cut list in
+                                       one chain: one scan, decode, segmented
+                                       sort and gather, sstable.write_tables;
+                                       recover_all(batched=True) goes through it
 
 A record is image[records[2i], records[2i] + records[2i+1]): one
 WriteBatch::rep_ (int64 {offset, length} pairs).  Entries are what block.decode
@@ -176,6 +184,33 @@ def sort(keys, key_offsets, stream=None):
     return PlanResult(source, out_off, counts, status)
 
 
+def sort_segments(keys, key_offsets, seg_first, stream=None):
+    """sort over the memtables of one log (lsbm_memtable_sort_segments_dev):
+    segment s = entries [seg_first[s], seg_first[s + 1]) (an int64 device
+    tensor that tiles the entries; empty segments are allowed).  Within a
+    segment the memtable's order; the segments stay in input order.  A
+    merge.PlanResult in sort's shape; a seg_first that does not tile gives
+    run_status MERGE_BAD_INPUT, counts {0, 0} and leaves `source` alone."""
+    torch = _torch()
+    _require_cuda(keys, key_offsets, seg_first)
+    _check(keys=keys, key_offsets=key_offsets, seg_first=seg_first)
+    n, ns = key_offsets.numel() - 1, seg_first.numel() - 1
+    if n < 0 or ns < 0:
+        raise ValueError("key_offsets and seg_first need at least one entry")
+    dev = keys.device
+    source = _buf(n, torch.int64, dev)
+    out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    scratch_bytes = lib().lsbm_memtable_sort_segments_scratch_bytes(n, ns)
+    scratch = torch.empty((scratch_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    check(lib().lsbm_memtable_sort_segments_dev(_ptr(keys), keys.numel(), _ptr(key_offsets), n, _ptr(seg_first), ns,
+                                                _ptr(source), _ptr(out_off), _ptr(counts), _ptr(status),
+                                                _ptr(scratch), scratch.numel() * 8, _stream_ptr(stream)),
+          "lsbm_memtable_sort_segments_dev")
+    return PlanResult(source, out_off, counts, status)
+
+
 def max_sequence_of(t):
     """The unsigned 64-bit number in decode's max_sequence tensor."""
     return int(t.cpu()[0]) & ((1 << 64) - 1)
@@ -240,6 +275,91 @@ def flush(image, records, compression=kNoCompression, block_size=4096, restart_i
     smallest = bytes(e.keys[:ends[0]].cpu().numpy())
     largest = bytes(e.keys[ends[1]:].cpu().numpy())
     return FlushResult(table, data_handles, index_handle, smallest, largest, e.max_sequence, e.status)
+
+
+def _max_sequences(image, records, mem_of, n_mems):
+    """Per memtable what decode's max_sequence holds for its records alone: the
+    largest Sequence + Count - 1 (unsigned; Count an int) over the records of
+    at least 12 bytes that lie inside the image; 0 without one.  int64[n_mems]
+    holding the 64 bits."""
+    torch = _torch()
+    rec = records.view(-1, 2)
+    off, ln = rec[:, 0], rec[:, 1]
+    size = image.numel()
+    ok = (off >= 0) & (ln >= 12) & (ln <= 0xffffffff) & (off <= size) & (ln <= size - off)
+    at = torch.where(ok, off, torch.zeros_like(off))[:, None] + torch.arange(12, device=image.device)
+    b = image[torch.where(ok[:, None], at, torch.zeros_like(at))].to(torch.int64) if size else \
+        torch.zeros_like(at)
+    seq = torch.zeros_like(off)
+    for i in range(8):
+        seq = seq | (b[:, i] << (8 * i))
+    count = b[:, 8] | (b[:, 9] << 8) | (b[:, 10] << 16) | (b[:, 11] << 24)
+    count = torch.where(count >= 1 << 31, count - (1 << 32), count)
+    flip = -(1 << 63)  # unsigned order as signed order
+    last = torch.where(ok, (seq + count - 1) ^ flip, torch.full_like(seq, flip))
+    best = torch.full((max(n_mems, 1),), flip, dtype=torch.int64, device=image.device)[:n_mems]
+    if last.numel():
+        best = best.scatter_reduce(0, mem_of, last, "amax", include_self=True)
+    return best ^ flip
+
+
+def flush_many(image, records, mem_first, compression=kNoCompression, block_size=4096, restart_interval=16,
+               bits_per_key=None, paranoid=False, stream=None):
+    """flush for the memtables of one cut list in one chain: memtable m is
+    records [mem_first[m], mem_first[m + 1]) (mem_first a list that tiles the
+    records).  One scan and one decode of all records, sort_segments, one
+    gather, sstable.write_tables.  Returns one FlushResult per memtable that has
+    at least one entry, each field what flush gives for that memtable's records
+    (image is a view of the chain's arena); memtables without an entry are
+    dropped before the table writer runs."""
+    torch = _torch()
+    from . import merge, sstable
+    from .block import INTERNAL_KEY
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return flush_many(image, records, mem_first, compression, block_size, restart_interval, bits_per_key,
+                              paranoid)
+    mem_first = [int(x) for x in mem_first]
+    n, n_mems = _n_records(records), len(mem_first) - 1
+    if n_mems < 0 or mem_first[0] != 0 or mem_first[-1] != n or any(a > b for a, b in zip(mem_first, mem_first[1:])):
+        raise ValueError("mem_first must tile the records")
+    if n_mems == 0:
+        return []
+    dev = image.device
+    counts, _ = scan(image, records)
+    entry_base, key_base = bases(counts)
+    d = decode(image, records, entry_base, key_base)
+    d_mem_first = torch.tensor(mem_first, dtype=torch.int64, device=dev)
+    seg_first = entry_base[d_mem_first].contiguous()
+    p = sort_segments(d.keys, d.key_offsets, seg_first)
+    g = merge.gather(d.keys, d.key_offsets, d.values.reshape(-1), p)
+    mem_of = torch.searchsorted(d_mem_first[1:].contiguous(), torch.arange(n, device=dev), right=True)
+    mem_of = torch.clamp(mem_of, max=n_mems - 1)
+    max_seq = _max_sequences(image, records, mem_of, n_mems)
+    # the one read after the chain: how many records are in error, sort's and gather's status, where the
+    # memtables' entries lie and their largest sequence numbers
+    host = torch.cat([torch.stack([(d.status != WB_OK).sum().to(torch.int64), p.run_status[0].to(torch.int64),
+                                   g.status[0].to(torch.int64)]), seg_first, max_seq]).cpu().tolist()
+    n_bad, sort_st, gather_st = host[:3]
+    seg_host, seq_host = host[3:4 + n_mems], host[4 + n_mems:]
+    if n_bad:  # (only then the statuses themselves)
+        status = d.status.cpu().tolist()
+        for r, st in enumerate(status):
+            if st in (WB_BAD_INPUT, WB_NO_ROOM) or (paranoid and st != WB_OK):
+                m = max(i for i in range(n_mems) if mem_first[i] <= r)
+                raise ValueError(f"record {r - mem_first[m]}: {STATUS_MESSAGE.get(st, st)}")
+    if sort_st != MERGE_OK or gather_st != MERGE_OK:
+        raise ValueError(f"internal error: sort status {sort_st}, gather status {gather_st}")
+    live = [m for m in range(n_mems) if seg_host[m + 1] > seg_host[m]]
+    if not live:
+        return []
+    # (the entries of the memtables without one are none: the live ones tile them)
+    table_first = [seg_host[m] for m in live] + [seg_host[-1]]
+    res = sstable.write_tables(g.keys, g.key_offsets, g.values.reshape(-1).contiguous(), image, table_first,
+                               INTERNAL_KEY, block_size, restart_interval, bits_per_key, compression)
+    return [FlushResult(res.table(t), res.table_data_handles(t), res.index_handle(t), res.smallest[t],
+                        res.largest[t], seq_host[m] & ((1 << 64) - 1), d.status[mem_first[m]:mem_first[m + 1]])
+            for t, m in enumerate(live)]
 
 
 def _framing(buf):
@@ -432,7 +552,7 @@ def cut(key_offsets, values, entry_base, mode, write_buffer_size, key_extra=0, t
 
 
 def recover_all(image, write_buffer_size=4 << 20, paranoid=False, compression=kNoCompression, block_size=4096,
-                restart_interval=16, bits_per_key=None, stream=None, log_bytes=None):
+                restart_interval=16, bits_per_key=None, stream=None, log_bytes=None, batched=False):
     """DBImpl::RecoverLogFile (lsbm/db_impl.cc:398-479) for a log of any size in
     device memory: log.read_records, scan, decode, cut in RECOVER mode, then
     one flush per memtable.  RecoverAllResult(flushes, mem_first, events,
@@ -444,13 +564,16 @@ def recover_all(image, write_buffer_size=4 << 20, paranoid=False, compression=kN
     paranoid=True: the loop ends at the reader's first report or at the first
     record WriteBatch::Iterate rejects (status: the reference's message); the
     tables of the memtables that ended before it are written, the memtable in
-    progress is not (RecoverLogFile returns before its WriteLevel0Table)."""
+    progress is not (RecoverLogFile returns before its WriteLevel0Table).
+
+    batched=True writes the tables of all memtables in one chain (flush_many)
+    instead of one flush each; the results are equal field by field."""
     torch = _torch()
     from . import log
     if stream is not None:
         with torch.cuda.stream(stream):
             return recover_all(image, write_buffer_size, paranoid, compression, block_size, restart_interval,
-                               bits_per_key, None, log_bytes)
+                               bits_per_key, None, log_bytes, batched)
     r = log.read_records(image, log_bytes)
     records, status = r.records, None
     if paranoid and r.events.shape[0]:
@@ -485,6 +608,14 @@ def recover_all(image, write_buffer_size=4 << 20, paranoid=False, compression=kN
     if cut_st != MERGE_OK:
         raise ValueError(f"internal error: cut status {cut_st}")
     mem_first = c.mem_first[:n_mem + 1].cpu().tolist()
+    if batched:
+        # (the loop ended early: the memtable in progress is not written)
+        n_done = n_mem - 1 if status is not None and n_mem and open_last else n_mem
+        # (records before the first memtable, too small to open one, belong to none)
+        flushes = flush_many(r.image, records[2 * mem_first[0]:2 * mem_first[n_done]].contiguous(),
+                             [m - mem_first[0] for m in mem_first[:n_done + 1]], compression, block_size,
+                             restart_interval, bits_per_key, False) if n_done else []
+        return RecoverAllResult(flushes, mem_first, r.events, status)
     flushes = []
     for m in range(n_mem):
         lo, hi = mem_first[m], mem_first[m + 1]

@@ -18,6 +18,18 @@ torch's current stream).
     table_get(image, index_handle, keys, key_offsets, ...)
                                        Table::InternalGet over either block type
     compact(images, ...)               merge.compact over either block type
+    pack_plan_tables, filter_layout, metaindex_blocks, place_tables
+                                       include/lsbm_table_write.h: the pack plan
+                                       restarting at every table, every table's
+                                       filter-block layout, metaindex block and
+                                       footer, and the handles at their bases
+    finish_tables(keys, key_offsets, block_first, table_block_first, blocks, ...)
+                                       TableBuilder from the first WriteBlock to
+                                       the footer for many tables in one chain
+    write_tables(keys, key_offsets, values, value_image, table_first, ...)
+                                       write_table for many tables at once; what
+                                       compact(batched=True) and
+                                       memtable.flush_many write through
 
 Handles are int64 {offset, size} pairs.  block.table_get, block_build.table_build
 and merge.compact keep their kNoCompression-only behaviour.
@@ -418,6 +430,367 @@ def write_table(keys, key_offsets, values, value_image, cmp=INTERNAL_KEY, block_
     return _finish_table(keys, key_offsets, block_first, blocks, cmp, restart_interval, bits_per_key, compression)
 
 
+# ---------------------------------------------------------------- many tables in one chain
+
+TABLE_ALIGN = 256         # finish_tables puts every table at a multiple of it
+FilterLayout = namedtuple("FilterLayout", "size count filter_first filter_out status")
+PlacedTables = namedtuple("PlacedTables", "table_size data_handles tail_handles status")
+
+
+class TablesResult(namedtuple("TablesResult", "arena table_handles data_handles table_block_first index_handles "
+                                              "smallest largest host")):
+    """finish_tables' result: every table of the chain in one arena.
+    table_handles int64[T, 2] = {base, size} in the arena (bases multiples of
+    TABLE_ALIGN, the bytes between tables zero); data_handles int64[2 n_blocks]
+    relative to their table, table t's being pairs [table_block_first[t],
+    table_block_first[t + 1]); index_handles int64[T, 2]; smallest / largest
+    every table's first and last key as bytes (None for a table without
+    entries).  host holds the host's copies of the three small tensors."""
+    __slots__ = ()
+
+    def table(self, t):
+        """Table t's file image: a view of the arena."""
+        base, size = (int(x) for x in self.host["table_handles"][t])
+        return self.arena[base:base + size]
+
+    def table_data_handles(self, t):
+        b0, b1 = (int(x) for x in self.host["table_block_first"][t:t + 2])
+        return self.data_handles[2 * b0:2 * b1]
+
+    def index_handle(self, t):
+        return tuple(int(x) for x in self.host["index_handles"][t])
+
+
+def _tw_scratch(n_blocks, n_tables, dev):
+    torch = _torch()
+    nbytes = int(lib().lsbm_table_write_scratch_bytes(n_blocks, n_tables))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+
+
+def _n_tables(table_block_first):
+    _i64(table_block_first, "table_block_first")
+    if table_block_first.numel() < 1:
+        raise ValueError("table_block_first needs n_tables + 1 entries")
+    return table_block_first.numel() - 1
+
+
+def pack_plan_tables(raw_len, comp_len, table_block_first, first_offset=None, gap=kBlockTrailerSize, types=None,
+                     handles=None, end=None, status=None, stream=None):
+    """pack_plan with the running offset restarting at every table
+    (lsbm_table_pack_plan_dev): (types uint8[n], handles int64[2n], end
+    int64[T], status int32[T])."""
+    torch = _torch()
+    _require_cuda(raw_len, comp_len, table_block_first, first_offset, types, handles, end, status)
+    _i64(raw_len, "raw_len")
+    n, nt, dev = raw_len.numel(), _n_tables(table_block_first), raw_len.device
+    for t, name, count in ((comp_len, "comp_len", n), (first_offset, "first_offset", nt)):
+        if t is not None:
+            _i64(t, name)
+            if t.numel() != count:
+                raise ValueError(f"{name} needs {count} entries")
+    from .engine import _buf
+    types = _buf(n, torch.uint8, dev) if types is None else types
+    handles = _buf(2 * n, torch.int64, dev) if handles is None else handles
+    end = _buf(nt, torch.int64, dev) if end is None else end
+    status = _buf(nt, torch.int32, dev) if status is None else status
+    if types.numel() != n or handles.numel() != 2 * n or end.numel() != nt or status.numel() != nt:
+        raise ValueError("types[n], handles[2n], end[T] and status[T] are needed")
+    scratch = _tw_scratch(n, nt, dev)
+    check(lib().lsbm_table_pack_plan_dev(_ptr(raw_len), _ptr(comp_len), n, _ptr(table_block_first), nt,
+                                         _ptr(first_offset), int(gap), _ptr(types), _ptr(handles), _ptr(end),
+                                         _ptr(status), _ptr(scratch), scratch.numel() * 8, _stream_ptr(stream)),
+          "lsbm_table_pack_plan_dev")
+    return types, handles, end, status
+
+
+def filter_layout(block_first, table_block_first, data_handles, data_end, bits_per_key, out=None, out_handles=None,
+                  filters_cap=0, stream=None):
+    """FilterBlockBuilder's layout for every table (lsbm_filter_layout_dev):
+    FilterLayout(size int64[T], count int64[T], filter_first, filter_out,
+    status int32[T]).  Without `out` only size and count; with it (and
+    out_handles, every table's filter-block window, filters_cap the sum of the
+    counts) filter_first / filter_out in bloom.build_filters' shape, and every
+    table's trailer written into its window."""
+    torch = _torch()
+    from .engine import _buf
+    _require_cuda(block_first, table_block_first, data_handles, data_end, out, out_handles)
+    for t, name in ((block_first, "block_first"), (data_handles, "data_handles"), (data_end, "data_end")):
+        _i64(t, name)
+    n, nt, dev = block_first.numel() - 1, _n_tables(table_block_first), block_first.device
+    if n < 0 or data_handles.numel() != 2 * n or data_end.numel() != nt:
+        raise ValueError("block_first[n + 1], data_handles[2n] and data_end[T] are needed")
+    if (out is None) != (out_handles is None):
+        raise ValueError("out and out_handles come together")
+    size, count, status = _buf(nt, torch.int64, dev), _buf(nt, torch.int64, dev), _buf(nt, torch.int32, dev)
+    first = out_f = None
+    if out is not None:
+        _u8(out, "out")
+        _i64(out_handles, "out_handles")
+        if out_handles.numel() != 2 * nt:
+            raise ValueError("out_handles needs one pair per table")
+        first, out_f = _buf(int(filters_cap) + 1, torch.int64, dev), _buf(int(filters_cap), torch.int64, dev)
+    scratch = _tw_scratch(n, nt, dev)
+    check(lib().lsbm_filter_layout_dev(_ptr(block_first), _ptr(table_block_first), n, nt, _ptr(data_handles),
+                                       _ptr(data_end), int(bits_per_key), _ptr(size), _ptr(count), _ptr(first),
+                                       _ptr(out_f), int(filters_cap) if out is not None else 0, _ptr(out),
+                                       out.numel() if out is not None else 0, _ptr(out_handles), _ptr(status),
+                                       _ptr(scratch), scratch.numel() * 8, _stream_ptr(stream)),
+          "lsbm_filter_layout_dev")
+    return FilterLayout(size, count, first, out_f, status)
+
+
+def metaindex_blocks(data_end, filter_size=None, out=None, out_handles=None, stream=None):
+    """One metaindex block per table (lsbm_metaindex_build_dev): (sizes
+    int64[T], status int32[T]); with out / out_handles the bytes too."""
+    torch = _torch()
+    from .engine import _buf
+    _require_cuda(data_end, filter_size, out, out_handles)
+    _i64(data_end, "data_end")
+    nt, dev = data_end.numel(), data_end.device
+    if filter_size is not None:
+        _i64(filter_size, "filter_size")
+    if (filter_size is not None and filter_size.numel() != nt) or (out is None) != (out_handles is None) or \
+            (out_handles is not None and out_handles.numel() != 2 * nt):
+        raise ValueError("filter_size[T], and out with out_handles[2T], are needed")
+    if out is not None:
+        _u8(out, "out")
+        _i64(out_handles, "out_handles")
+    sizes, status = _buf(nt, torch.int64, dev), _buf(nt, torch.int32, dev)
+    check(lib().lsbm_metaindex_build_dev(_ptr(data_end), _ptr(filter_size), nt, _ptr(sizes), _ptr(out),
+                                         out.numel() if out is not None else 0, _ptr(out_handles), _ptr(status),
+                                         _stream_ptr(stream)), "lsbm_metaindex_build_dev")
+    return sizes, status
+
+
+def place_tables(data_handles, table_block_first, tail_handles, tail_per_table, tail_end, table_base, arena,
+                 stream=None):
+    """Footers and placement (lsbm_table_place_dev): PlacedTables(table_size
+    int64[T], data_handles, tail_handles with their table's base added, status
+    int32[T]); every table's footer is written into `arena`."""
+    torch = _torch()
+    from .engine import _buf
+    _require_cuda(data_handles, table_block_first, tail_handles, tail_end, table_base, arena)
+    for t, name in ((data_handles, "data_handles"), (tail_handles, "tail_handles"), (tail_end, "tail_end"),
+                    (table_base, "table_base")):
+        _i64(t, name)
+    _u8(arena, "arena")
+    nt, dev = _n_tables(table_block_first), arena.device
+    n, k = data_handles.numel() // 2, int(tail_per_table)
+    if data_handles.numel() % 2 or tail_handles.numel() != 2 * k * nt or tail_end.numel() != nt or \
+            table_base.numel() != nt:
+        raise ValueError("data_handles[2n], tail_handles[2 k T], tail_end[T] and table_base[T] are needed")
+    size, status = _buf(nt, torch.int64, dev), _buf(nt, torch.int32, dev)
+    abs_d, abs_t = _buf(2 * n, torch.int64, dev), _buf(2 * k * nt, torch.int64, dev)
+    scratch = _tw_scratch(n, nt, dev)
+    check(lib().lsbm_table_place_dev(_ptr(data_handles), n, _ptr(table_block_first), _ptr(tail_handles), k,
+                                     _ptr(tail_end), _ptr(table_base), nt, _ptr(arena), arena.numel(), _ptr(size),
+                                     _ptr(abs_d), _ptr(abs_t), _ptr(status), _ptr(scratch), scratch.numel() * 8,
+                                     _stream_ptr(stream)), "lsbm_table_place_dev")
+    return PlacedTables(size, abs_d, abs_t, status)
+
+
+def _worst(*statuses):
+    """The largest word of some status tensors, as an int64[1] for a read that is due anyway."""
+    torch = _torch()
+    live = [s.reshape(-1).to(torch.int64) for s in statuses if s is not None and s.numel()]
+    return torch.cat(live).max().reshape(1) if live else None
+
+
+def finish_tables(keys, key_offsets, block_first, table_block_first, blocks, cmp=INTERNAL_KEY, restart_interval=16,
+                  bits_per_key=None, compression=kSnappyCompression, stream=None):
+    """TableBuilder from the first WriteBlock to the footer for every table of
+    a batch at once, over data blocks that are already built (and compressed):
+    block b = entries [block_first[b], block_first[b + 1]) of keys /
+    key_offsets, table t = blocks [table_block_first[t], table_block_first[t +
+    1]) (device tensors; `blocks` a _Blocks over all of them).  The pack plan
+    restarts at every table, the filter blocks are laid out and built on the
+    device, every metaindex and index block is built in one call each, the tail
+    blocks are compressed and ruled together, and one pack and one seal per kind
+    put every block of every table into one arena.  Returns a TablesResult.
+    The host reads a fixed number of times, whatever the number of tables or
+    blocks: the staging sizes, the arena's size, and the results."""
+    torch = _torch()
+    from . import block_build, bloom, snappy
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return finish_tables(keys, key_offsets, block_first, table_block_first, blocks, cmp, restart_interval,
+                                 bits_per_key, compression)
+    if compression not in (kNoCompression, kSnappyCompression):
+        raise ValueError("unknown compression type")
+    if cmp not in (BYTEWISE, INTERNAL_KEY):
+        raise ValueError("unknown comparator")
+    _require_cuda(keys, key_offsets, block_first, table_block_first)
+    dev = keys.device
+    nb, nt = block_first.numel() - 1, _n_tables(table_block_first)
+    if nb < 0 or nt < 1:
+        raise ValueError("block_first needs n_blocks + 1 entries and table_block_first at least one table")
+    snappy_on = compression == kSnappyCompression
+    zeros = lambda n: torch.zeros(max(n, 1), dtype=torch.int64, device=dev)[:n]  # noqa: E731
+    # 1. WriteBlock's rule over the data blocks, the offsets restarting at every table
+    raw_len = blocks.raw_handles.view(-1, 2)[:, 1].contiguous() if nb else zeros(0)
+    d_types, d_handles, data_end, st_plan = pack_plan_tables(raw_len, blocks.comp_len if snappy_on and nb else None,
+                                                             table_block_first)
+    # 2. the sizes of the blocks that follow: [filter,] metaindex, index
+    k = 3 if bits_per_key is not None else 2
+    fsize = fcount = st_lay = None
+    if bits_per_key is not None:
+        lay = filter_layout(block_first, table_block_first, d_handles, data_end, int(bits_per_key))
+        fsize, fcount, st_lay = lay.size, lay.count, lay.status
+    msize, st_meta = metaindex_blocks(data_end, fsize)
+    isize, st_index = block_build.index_block(keys, key_offsets, block_first, table_block_first, d_handles, cmp)
+    tail_raw_len = torch.stack(([fsize] if k == 3 else []) + [msize, isize], 1).reshape(-1).contiguous() if nt else \
+        zeros(0)
+    tail_offsets = zeros(k * nt + 1)
+    if nt:
+        torch.cumsum(tail_raw_len, 0, out=tail_offsets[1:])
+    # the first read: the staging image's size and the filters
+    head = torch.cat([tail_offsets[-1:], fcount.sum().reshape(1) if k == 3 and nt else zeros(1),
+                      _worst(st_plan, st_lay, st_meta, st_index) if nt else zeros(1)]).cpu().tolist()
+    tail_total, n_filters, worst = (int(x) for x in head)
+    if worst:
+        for st, what in ((st_plan, "table pack plan"), (st_lay, "filter layout"), (st_meta, "metaindex block"),
+                         (st_index, "index block")):
+            if st is not None:
+                _raise_on(st, what)
+    tail = torch.zeros(max(tail_total, 1), dtype=torch.uint8, device=dev)[:tail_total]
+    tail_raw_handles = torch.stack([tail_offsets[:-1], tail_raw_len], 1).contiguous() if nt else zeros(0).view(0, 2)
+    window = lambda j: tail_raw_handles.view(nt, k, 2)[:, j].reshape(-1).contiguous()  # noqa: E731
+    # 3. the filter blocks: layout and trailers, then every filter of every table in one launch
+    st_room = []
+    if k == 3 and nt:
+        lay = filter_layout(block_first, table_block_first, d_handles, data_end, int(bits_per_key), tail, window(0),
+                            n_filters)
+        if int(_worst(lay.status).cpu()[0]):  # (a filter without a place must not reach the bloom kernel)
+            _raise_on(lay.status, "filter layout")
+        if n_filters:
+            bloom.build_filters(keys, key_offsets, lay.filter_first, lay.filter_out, tail, int(bits_per_key),
+                                strip=8 if cmp == INTERNAL_KEY else 0)
+    # 4. the metaindex blocks and 5. the index blocks
+    if nt:
+        st_room.append(metaindex_blocks(data_end, fsize, tail, window(k - 2))[1])
+        st_room.append(block_build.index_block(keys, key_offsets, block_first, table_block_first, d_handles, cmp,
+                                               tail, window(k - 1))[1])
+    # WriteBlock's rule over them; the filter block is WriteRawBlock(kNoCompression)
+    tail_comp = tail_comp_offsets = tail_comp_len = None
+    if snappy_on and nt:
+        tail_comp, tail_comp_offsets, tail_comp_len = snappy.compress(tail, tail_offsets)
+        tail_comp_offsets = tail_comp_offsets[:-1].contiguous()
+        tail_comp_len = tail_comp_len.clone()
+        if k == 3:
+            tail_comp_len.view(nt, k)[:, 0] = COMP_NONE
+    tail_first = torch.arange(nt + 1, dtype=torch.int64, device=dev) * k
+    t_types, t_handles, tail_end, st_tail = pack_plan_tables(tail_raw_len, tail_comp_len, tail_first, data_end)
+    # 6. every table's place in the arena: the second read
+    table_size = tail_end + block_build.kFooterEncodedLength
+    padded = (table_size + (TABLE_ALIGN - 1)) // TABLE_ALIGN * TABLE_ALIGN
+    table_base = zeros(nt + 1)
+    if nt:
+        torch.cumsum(padded, 0, out=table_base[1:])
+    total, worst = (int(x) for x in torch.cat([table_base[-1:], _worst(st_tail, *st_room) if nt else
+                                               zeros(1)]).cpu().tolist())
+    if worst:
+        for st, what in zip([st_tail] + st_room, ("tail pack plan", "metaindex block", "index block")):
+            _raise_on(st, what)
+    arena = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)[:total]
+    table_base = table_base[:-1].contiguous()
+    placed = place_tables(d_handles, table_block_first, t_handles, k, tail_end, table_base, arena)
+    # 7. everything to its place, every trailer
+    st_pack = [placed.status]
+    if nb:
+        st_pack.append(pack(blocks.raw, blocks.raw_handles, blocks.comp if snappy_on else None,
+                            blocks.comp_offsets if snappy_on else None, d_types, placed.data_handles, arena))
+    if nt:
+        st_pack.append(pack(tail, tail_raw_handles.reshape(-1), tail_comp, tail_comp_offsets, t_types,
+                            placed.tail_handles, arena))
+        seal_blocks(arena, torch.cat([placed.data_handles, placed.tail_handles]).contiguous(),
+                    torch.cat([d_types, t_types]).contiguous())
+    # the third read: the results, and where every table's first and last key lie
+    table_handles = torch.stack([table_base, table_size], 1) if nt else zeros(0).view(0, 2)
+    index_handles = t_handles.view(nt, k, 2)[:, k - 1].contiguous() if nt else zeros(0).view(0, 2)
+    e0 = block_first[table_block_first[:-1]]
+    e1 = block_first[table_block_first[1:]]
+    last = torch.clamp(e1 - 1, min=0)
+    key_at = torch.stack([key_offsets[e0], key_offsets[torch.clamp(e0 + 1, max=key_offsets.numel() - 1)],
+                          key_offsets[last], key_offsets[e1]], 1) if nt else zeros(0).view(0, 4)
+    host = torch.cat([table_handles.reshape(-1), index_handles.reshape(-1), table_block_first, e0, e1,
+                      key_at.reshape(-1), _worst(*st_pack) if nt else zeros(1)]).cpu().numpy()
+    th, ih = host[:2 * nt].reshape(nt, 2), host[2 * nt:4 * nt].reshape(nt, 2)
+    tbf_host = host[4 * nt:5 * nt + 1]
+    e0_host, e1_host = host[5 * nt + 1:6 * nt + 1], host[6 * nt + 1:7 * nt + 1]
+    ka = host[7 * nt + 1:11 * nt + 1].reshape(nt, 4)
+    if int(host[-1]):
+        for st, what in zip(st_pack, ("table placement", "pack", "pack")):
+            _raise_on(st, what)
+    # the fourth read: those keys' bytes, gathered on the device
+    smallest, largest = [None] * nt, [None] * nt
+    live = [t for t in range(nt) if e1_host[t] > e0_host[t]]
+    if live:
+        spans = [(int(ka[t][0]), int(ka[t][1])) for t in live] + [(int(ka[t][2]), int(ka[t][3])) for t in live]
+        at = np.concatenate([np.arange(lo, hi, dtype=np.int64) for lo, hi in spans])
+        got = keys[torch.from_numpy(at).to(dev)].cpu().numpy().tobytes()
+        pos = 0
+        for j, (lo, hi) in enumerate(spans):
+            (smallest if j < len(live) else largest)[live[j % len(live)]] = got[pos:pos + hi - lo]
+            pos += hi - lo
+    return TablesResult(arena, table_handles, d_handles, table_block_first, index_handles, smallest, largest,
+                        {"table_handles": th, "index_handles": ih, "table_block_first": tbf_host})
+
+
+def write_tables(keys, key_offsets, values, value_image, table_first, cmp=INTERNAL_KEY, block_size=4096,
+                 restart_interval=16, bits_per_key=None, compression=kSnappyCompression, stream=None):
+    """write_table for many tables in one chain: table t = entries
+    [table_first[t], table_first[t + 1]) (an int64 device tensor or a list;
+    the tables tile the entries).  Plan, build and compress as write_table does
+    them, over all tables at once, then finish_tables.  A table without entries
+    is the file write_table writes for no entries.  Returns a TablesResult."""
+    torch = _torch()
+    from . import block_build
+    if compression not in (kNoCompression, kSnappyCompression):
+        raise ValueError("unknown compression type")
+    if cmp not in (BYTEWISE, INTERNAL_KEY):
+        raise ValueError("unknown comparator")
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return write_tables(keys, key_offsets, values, value_image, table_first, cmp, block_size,
+                                restart_interval, bits_per_key, compression)
+    _require_cuda(keys, key_offsets, values, value_image)
+    dev = keys.device
+    n = key_offsets.numel() - 1
+    if n < 0 or values.numel() != 2 * n:
+        raise ValueError("values must be one {offset, length} pair per entry")
+    values = values.reshape(-1)
+    if not hasattr(table_first, "is_cuda"):
+        table_first = torch.tensor([int(x) for x in table_first], dtype=torch.int64, device=dev)
+    _require_cuda(table_first)
+    p = block_build.plan(keys, key_offsets, values, table_first, block_size, restart_interval)
+    # the one read of the plan: its status, the number of blocks, their bytes
+    worst, nb, total = (int(x) for x in torch.cat([_worst(p.status) if p.status.numel() else
+                                                   torch.zeros(1, dtype=torch.int64, device=dev),
+                                                   p.table_block_first[-1:], p.block_bytes.sum().reshape(1)])
+                        .cpu().tolist())
+    if worst:
+        block_build._raise_on(p.status, "plan")
+    block_first = p.block_first[:nb + 1].contiguous()
+    sizes = p.block_bytes[:nb]
+    offsets = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+    if nb:
+        torch.cumsum(sizes, 0, out=offsets[1:])
+    raw = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)[:total]
+    raw_handles = torch.stack([offsets[:-1], sizes], 1).reshape(-1).contiguous()
+    blocks = _Blocks(raw, raw_handles, None, None, None)
+    if nb:
+        _, st = block_build.build(keys, key_offsets, values, value_image, block_first, raw, raw_handles,
+                                  restart_interval)
+        if int(_worst(st).cpu()[0]):
+            block_build._raise_on(st, "build")
+        if compression == kSnappyCompression:
+            from . import snappy
+            comp, comp_offsets, comp_len = snappy.compress(raw, offsets)
+            blocks = _Blocks(raw, raw_handles, comp, comp_offsets[:-1].contiguous(), comp_len.contiguous())
+    return finish_tables(keys, key_offsets, block_first, p.table_block_first, blocks, cmp, restart_interval,
+                         bits_per_key, compression)
+
+
 # ---------------------------------------------------------------- Get
 
 
@@ -524,7 +897,7 @@ def index_data_handles(image, index_handle, verify=True):
 
 def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None, cmp=INTERNAL_KEY, drop=False,
             smallest_snapshot=None, bottom_level=False, block_size=4096, restart_interval=16, bits_per_key=None,
-            compression=kNoCompression, verify=True, stream=None):
+            compression=kNoCompression, verify=True, stream=None, batched=False):
     """merge.compact for tables whose blocks are of either type, with output
     tables written under `compression`.  Every input data block goes through
     read_blocks, whose contents are the value image that decode, merge and the
@@ -532,13 +905,16 @@ def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None
     data block of that plan is built and compressed once; the cut
     (merge.cut_tables) sees each block's packed size, as FileSize() does; and
     each output table is finished from its slice of those blocks.  Returns
-    [OutputTable(image, data_handles, index_handle)]."""
+    [OutputTable(image, data_handles, index_handle)].  batched=True finishes
+    every output table in one chain (finish_tables): the images are views of
+    one arena and their bytes are the same."""
     torch = _torch()
     from . import block, block_build, merge
     if stream is not None:
         with torch.cuda.stream(stream):
             return compact(images, data_handles, max_file_size, index_handles, cmp, drop, smallest_snapshot,
-                           bottom_level, block_size, restart_interval, bits_per_key, compression, verify)
+                           bottom_level, block_size, restart_interval, bits_per_key, compression, verify, None,
+                           batched)
     if (data_handles is None) == (index_handles is None):
         raise ValueError("give data_handles or index_handles")
     if compression not in (kNoCompression, kSnappyCompression):
@@ -605,6 +981,12 @@ def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None
     _, packed, _ = pack_plan(blocks.raw_handles.view(-1, 2)[:, 1].contiguous(), blocks.comp_len)
     table_first, table_block_first = merge.cut_tables(first_host, packed.view(-1, 2)[:, 1].cpu().tolist(),
                                                       int(max_file_size))
+    if batched:  # 5. every output table in one chain
+        res = finish_tables(m.keys, m.key_offsets, block_first,
+                            torch.tensor(table_block_first, dtype=torch.int64, device=dev), blocks, cmp,
+                            restart_interval, bits_per_key, compression)
+        return [OutputTable(res.table(t), res.table_data_handles(t), res.index_handle(t))
+                for t in range(len(table_first) - 1)]
     # 5. each output table from its slice of the entries and of the blocks
     out = []
     key_at = m.key_offsets[torch.tensor(table_first, dtype=torch.int64, device=dev)].cpu().tolist()
