@@ -13,7 +13,8 @@
   lsbm_amd.merge    compaction merge: batched MergingIterator over sorted runs, DoCompactionWork's
                     drop rule and output-file cut, input table images -> output table files
   lsbm_amd.sstable  tables with snappy-compressed blocks: WriteBlock's keep rule and block packing,
-                    batched ReadBlock, table writer, Get and compaction over either block type
+                    batched ReadBlock, Get and compaction over either block type, and the one table
+                    writer (write_tables / finish_tables) that block_build, merge and memtable write through
   lsbm_amd.memtable memtable flush: batched WriteBatch::Iterate over log records, the memtable's
                     iteration order as a sort, log image -> Level-0 table file (recover: RecoverLogFile
                     over a log in device memory)

@@ -15,7 +15,8 @@ tensors out; every call enqueues on `stream` (default: torch's current stream).
                                       one index block per table: separators,
                                       successor, BlockHandle::EncodeTo
     table_build(keys, key_offsets, values, value_image, ...)
-                                      one complete kNoCompression table file
+                                      one complete kNoCompression table file:
+                                      sstable.write_table without compression
 
 Entries are what block.decode returns: a uint8 key buffer plus int64 offsets
 (key e = keys[off[e], off[e+1])) and int64 {offset, length} value slices of
@@ -23,12 +24,10 @@ Entries are what block.decode returns: a uint8 key buffer plus int64 offsets
 """
 from collections import namedtuple
 
-import numpy as np
-
 from ._lib import check, lib
-from .block import BYTEWISE, INTERNAL_KEY
+from .block import INTERNAL_KEY
 from .engine import _check_tensors, _ptr, _raise_on as _raise_on_status, _require_cuda, _stream_ptr, _torch
-from .table import kNoCompression, layout_blocks, seal_blocks
+from .table import kNoCompression
 
 # per-block / per-table status (include/lsbm_block_build.h)
 BUILD_OK = 0
@@ -57,20 +56,6 @@ def _n_entries(key_offsets, values=None):
     if values is not None and values.numel() != 2 * n:
         raise ValueError("values must be one {offset, length} pair per entry")
     return n
-
-
-def put_varint64(v):
-    out = bytearray()
-    while v >= 128:
-        out.append((v & 127) | 128)
-        v >>= 7
-    out.append(v)
-    return bytes(out)
-
-
-def encode_handle(offset, size):
-    """BlockHandle::EncodeTo (table/format.cc:15-21)."""
-    return put_varint64(int(offset)) + put_varint64(int(size))
 
 
 def plan(keys, key_offsets, values, table_first, block_size=4096, restart_interval=16, blocks_cap=None,
@@ -159,98 +144,18 @@ def _raise_on(status, what):
     _raise_on_status(status, what, BUILD_OK, STATUS_MESSAGE)
 
 
-def footer(metaindex_handle, index_handle):
-    """Footer::EncodeTo (table/format.cc:32-42)."""
-    enc = encode_handle(*metaindex_handle) + encode_handle(*index_handle)
-    return enc + bytes(40 - len(enc)) + kTableMagicNumber.to_bytes(8, "little")
-
-
 def table_build(keys, key_offsets, values, value_image, cmp=INTERNAL_KEY, block_size=4096,
                 restart_interval=16, bits_per_key=None, compression=kNoCompression, stream=None):
     """TableBuilder (table/table_builder.cc) Add for every entry, then Finish,
     for one complete table file: data blocks, the filter block
     (BloomFilterPolicy(bits_per_key); InternalFilterPolicy under INTERNAL_KEY),
     the metaindex block, the index block, every trailer and the footer
-    (kNoCompression only; sstable.write_table writes snappy-compressed tables).
-    Returns (file_image uint8 device tensor, data_handles int64 device tensor of
-    {offset, size} pairs, index_handle (offset, size))."""
-    torch = _torch()
-    from . import bloom
+    (kNoCompression only; sstable.write_table writes snappy-compressed tables,
+    and this is it with compression=kNoCompression).  Returns (file_image uint8
+    device tensor, data_handles int64 device tensor of {offset, size} pairs,
+    index_handle (offset, size))."""
+    from . import sstable
     if compression != kNoCompression:
         raise ValueError("table_build writes kNoCompression tables only")
-    if cmp not in (BYTEWISE, INTERNAL_KEY):
-        raise ValueError("unknown comparator")
-    if stream is not None:  # (the copies between the steps are torch's: on the same stream)
-        with torch.cuda.stream(stream):
-            return table_build(keys, key_offsets, values, value_image, cmp, block_size, restart_interval,
-                               bits_per_key, compression)
-    _require_cuda(keys, key_offsets, values, value_image)
-    dev = keys.device
-    n = _n_entries(key_offsets, values)
-    # 1.-2. where the blocks end, and their sizes (the one read of the plan)
-    table_first = torch.tensor([0, n], dtype=torch.int64, device=dev)
-    p = plan(keys, key_offsets, values, table_first, block_size, restart_interval)
-    _raise_on(p.status, "plan")
-    nb = int(p.table_block_first[-1])
-    sizes = p.block_bytes[:nb].cpu().numpy()
-    block_first = p.block_first[:nb + 1].contiguous()
-    first_host = block_first.cpu().numpy()
-    # 3. the data blocks' places; the blocks after them follow below
-    data_handles, data_end = layout_blocks(sizes)
-    # 5. the filter block (host bytes: its offset array is laid out on the host)
-    filt = None
-    if bits_per_key is not None:
-        # (the last Flush's StartBlock(offset after the last block): a block without keys)
-        starts = list(data_handles[0::2]) + ([data_end] if nb else [])
-        firsts = list(first_host) + ([n] if nb else [])
-        filt = bloom.build_filter_block(keys, key_offsets, starts, firsts, int(bits_per_key),
-                                        strip=8 if cmp == INTERNAL_KEY else 0)
-    # 6. the metaindex block's one entry
-    if filt is not None:
-        meta_value = encode_handle(data_end, len(filt))
-        m_keys = torch.tensor(list(FILTER_KEY), dtype=torch.uint8, device=dev)
-        m_off = torch.tensor([0, len(FILTER_KEY)], dtype=torch.int64, device=dev)
-        m_values = torch.tensor([0, len(meta_value)], dtype=torch.int64, device=dev)
-        m_image = torch.tensor(list(meta_value), dtype=torch.uint8, device=dev)
-        m_first = torch.tensor([0, 1], dtype=torch.int64, device=dev)
-        meta_size = 3 + len(FILTER_KEY) + len(meta_value) + 8
-    else:
-        m_keys = torch.zeros(0, dtype=torch.uint8, device=dev)
-        m_off = torch.zeros(1, dtype=torch.int64, device=dev)
-        m_values = torch.zeros(0, dtype=torch.int64, device=dev)
-        m_image = torch.zeros(0, dtype=torch.uint8, device=dev)
-        m_first = torch.zeros(2, dtype=torch.int64, device=dev)
-        meta_size = 8
-    # 7. the index block's size
-    d_handles = torch.from_numpy(data_handles).to(dev)
-    tbf = torch.tensor([0, nb], dtype=torch.int64, device=dev)
-    isize, ist = index_block(keys, key_offsets, block_first, tbf, d_handles, cmp)
-    _raise_on(ist, "index block")
-    index_size = int(isize[0])
-    # the whole file: data blocks, [filter], metaindex, index, each with its trailer, and the footer
-    all_sizes = list(sizes) + ([len(filt)] if filt is not None else []) + [meta_size, index_size]
-    handles, end = layout_blocks(all_sizes)
-    image = torch.zeros(end + kFooterEncodedLength, dtype=torch.uint8, device=dev)
-    # 4. the data blocks, straight into the file image
-    _, st = build(keys, key_offsets, values, value_image, block_first, image, d_handles, restart_interval)
-    _raise_on(st, "build")
-    k = nb
-    if filt is not None:
-        image[int(handles[2 * k]):int(handles[2 * k]) + len(filt)] = torch.from_numpy(
-            np.frombuffer(filt, dtype=np.uint8).copy()).to(dev)
-        k += 1
-    meta_handle = (int(handles[2 * k]), int(handles[2 * k + 1]))
-    index_handle = (int(handles[2 * k + 2]), int(handles[2 * k + 3]))
-    _, st = build(m_keys, m_off, m_values, m_image, m_first, image,
-                  torch.tensor(meta_handle, dtype=torch.int64, device=dev), restart_interval)
-    _raise_on(st, "metaindex block")
-    _, st = index_block(keys, key_offsets, block_first, tbf, d_handles, cmp, image,
-                        torch.tensor(index_handle, dtype=torch.int64, device=dev))
-    _raise_on(st, "index block")
-    # 8. every trailer
-    d_all = torch.from_numpy(handles).to(dev)
-    seal_blocks(image, d_all, torch.full((len(all_sizes),), kNoCompression, dtype=torch.uint8, device=dev))
-    # 9. the footer
-    image[end:] = torch.tensor(list(footer(meta_handle, index_handle)), dtype=torch.uint8, device=dev)
-    return image, d_handles, index_handle
-
+    return sstable.write_table(keys, key_offsets, values, value_image, cmp, block_size, restart_interval,
+                               bits_per_key, kNoCompression, stream)

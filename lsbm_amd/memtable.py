@@ -15,8 +15,8 @@ torch's current stream).
                                        merge.PlanResult (merge.gather gathers it)
     entries(image, records, ...)       scan + decode + sort + gather: what
                                        MemTable::NewIterator() returns
-    flush(image, records, ...)         entries, then sstable.write_table: the
-                                       Level-0 table file (BuildTable)
+    flush(image, records, ...)         entries, then sstable.write_tables of one
+                                       table: the Level-0 table file (BuildTable)
     log_records(image_host)            a log file's logical records as
                                        {offset, length} pairs, fragments
                                        assembled on the device
@@ -38,7 +38,7 @@ torch's current stream).
                                        flush of every memtable of a cut list in
                                        one chain: one scan, decode, segmented
                                        sort and gather, sstable.write_tables;
-                                       recover_all(batched=True) goes through it
+                                       recover_all goes through it
 
 A record is image[records[2i], records[2i] + records[2i+1]): one
 WriteBatch::rep_ (int64 {offset, length} pairs).  Entries are what block.decode
@@ -256,8 +256,9 @@ def flush(image, records, compression=kNoCompression, block_size=4096, restart_i
     max_sequence, status).  image is the Level-0 table file (a uint8 device
     tensor) with the internal-key comparator and, with bits_per_key, the
     InternalFilterPolicy bloom; smallest / largest are the first and the last
-    internal key as bytes (FileMetaData).  Without an entry no table is written:
-    image, data_handles, index_handle, smallest and largest are None."""
+    internal key as bytes (FileMetaData), as the table writer's TablesResult
+    has them.  Without an entry no table is written: image, data_handles,
+    index_handle, smallest and largest are None."""
     torch = _torch()
     from . import sstable
     from .block import INTERNAL_KEY
@@ -269,12 +270,10 @@ def flush(image, records, compression=kNoCompression, block_size=4096, restart_i
     if n == 0:
         return FlushResult(None, None, None, None, None, e.max_sequence, e.status)
     values = e.values.reshape(-1).contiguous()
-    table, data_handles, index_handle = sstable.write_table(e.keys, e.key_offsets, values, image, INTERNAL_KEY,
-                                                            block_size, restart_interval, bits_per_key, compression)
-    ends = e.key_offsets[torch.tensor([1, n - 1], device=e.key_offsets.device)].cpu().tolist()
-    smallest = bytes(e.keys[:ends[0]].cpu().numpy())
-    largest = bytes(e.keys[ends[1]:].cpu().numpy())
-    return FlushResult(table, data_handles, index_handle, smallest, largest, e.max_sequence, e.status)
+    res = sstable.write_tables(e.keys, e.key_offsets, values, image, [0, n], INTERNAL_KEY, block_size,
+                               restart_interval, bits_per_key, compression)
+    return FlushResult(res.table(0), res.table_data_handles(0), res.index_handle(0), res.smallest[0], res.largest[0],
+                       e.max_sequence, e.status)
 
 
 def _max_sequences(image, records, mem_of, n_mems):
@@ -310,8 +309,9 @@ def flush_many(image, records, mem_first, compression=kNoCompression, block_size
     records).  One scan and one decode of all records, sort_segments, one
     gather, sstable.write_tables.  Returns one FlushResult per memtable that has
     at least one entry, each field what flush gives for that memtable's records
-    (image is a view of the chain's arena); memtables without an entry are
-    dropped before the table writer runs."""
+    (the images are views of the chain's one arena, so holding one keeps the
+    whole arena alive); memtables without an entry are dropped before the table
+    writer runs."""
     torch = _torch()
     from . import merge, sstable
     from .block import INTERNAL_KEY
@@ -552,28 +552,27 @@ def cut(key_offsets, values, entry_base, mode, write_buffer_size, key_extra=0, t
 
 
 def recover_all(image, write_buffer_size=4 << 20, paranoid=False, compression=kNoCompression, block_size=4096,
-                restart_interval=16, bits_per_key=None, stream=None, log_bytes=None, batched=False):
+                restart_interval=16, bits_per_key=None, stream=None, log_bytes=None):
     """DBImpl::RecoverLogFile (lsbm/db_impl.cc:398-479) for a log of any size in
     device memory: log.read_records, scan, decode, cut in RECOVER mode, then
-    one flush per memtable.  RecoverAllResult(flushes, mem_first, events,
-    status): flushes are the FlushResults in file order (a memtable without an
-    entry writes no table and has none), mem_first the first record of every
+    flush_many: the tables of all memtables are written in one chain.
+    RecoverAllResult(flushes, mem_first, events, status): flushes are the
+    FlushResults in file order (a memtable without an entry writes no table and
+    has none; the images are views of one arena that holds every table of the
+    log, so holding one keeps the whole arena alive), mem_first the first record of every
     memtable closed by the count of the records the loop took (a list), events
     and status as recover gives them.  write_buffer_size is clipped as SanitizeOptions clips it.
 
     paranoid=True: the loop ends at the reader's first report or at the first
     record WriteBatch::Iterate rejects (status: the reference's message); the
     tables of the memtables that ended before it are written, the memtable in
-    progress is not (RecoverLogFile returns before its WriteLevel0Table).
-
-    batched=True writes the tables of all memtables in one chain (flush_many)
-    instead of one flush each; the results are equal field by field."""
+    progress is not (RecoverLogFile returns before its WriteLevel0Table)."""
     torch = _torch()
     from . import log
     if stream is not None:
         with torch.cuda.stream(stream):
             return recover_all(image, write_buffer_size, paranoid, compression, block_size, restart_interval,
-                               bits_per_key, None, log_bytes, batched)
+                               bits_per_key, None, log_bytes)
     r = log.read_records(image, log_bytes)
     records, status = r.records, None
     if paranoid and r.events.shape[0]:
@@ -608,21 +607,10 @@ def recover_all(image, write_buffer_size=4 << 20, paranoid=False, compression=kN
     if cut_st != MERGE_OK:
         raise ValueError(f"internal error: cut status {cut_st}")
     mem_first = c.mem_first[:n_mem + 1].cpu().tolist()
-    if batched:
-        # (the loop ended early: the memtable in progress is not written)
-        n_done = n_mem - 1 if status is not None and n_mem and open_last else n_mem
-        # (records before the first memtable, too small to open one, belong to none)
-        flushes = flush_many(r.image, records[2 * mem_first[0]:2 * mem_first[n_done]].contiguous(),
-                             [m - mem_first[0] for m in mem_first[:n_done + 1]], compression, block_size,
-                             restart_interval, bits_per_key, False) if n_done else []
-        return RecoverAllResult(flushes, mem_first, r.events, status)
-    flushes = []
-    for m in range(n_mem):
-        lo, hi = mem_first[m], mem_first[m + 1]
-        if status is not None and m == n_mem - 1 and open_last:
-            break  # the loop ended early: the memtable in progress is not written
-        f = flush(r.image, records[2 * lo:2 * hi].contiguous(), compression, block_size, restart_interval,
-                  bits_per_key, False)
-        if f.image is not None:
-            flushes.append(f)
+    # (the loop ended early: the memtable in progress is not written)
+    n_done = n_mem - 1 if status is not None and n_mem and open_last else n_mem
+    # (records before the first memtable, too small to open one, belong to none)
+    flushes = flush_many(r.image, records[2 * mem_first[0]:2 * mem_first[n_done]].contiguous(),
+                         [m - mem_first[0] for m in mem_first[:n_done + 1]], compression, block_size,
+                         restart_interval, bits_per_key, False) if n_done else []
     return RecoverAllResult(flushes, mem_first, r.events, status)

@@ -18,7 +18,9 @@ out; every call enqueues on `stream` (default: torch's current stream).
                                       files (host arithmetic over a plan)
     compact(images, data_handles, max_file_size, ...)
                                       input table images -> output table files:
-                                      scan, decode, merge, plan, cut, table_build
+                                      scan, decode, merge, plan, cut and
+                                      sstable.finish_tables (one body with
+                                      sstable.compact)
 
 Entries are what block.decode returns and block_build reads: a uint8 key buffer
 plus int64 offsets and int64 {offset, length} value slices.  Run r owns entries
@@ -26,11 +28,10 @@ plus int64 offsets and int64 {offset, length} value slices.  Run r owns entries
 """
 from collections import namedtuple
 
-import numpy as np
-
 from ._lib import check, lib
 from .block import BYTEWISE, INTERNAL_KEY
-from .engine import _check_tensors, _ptr, _raise_on, _require_cuda, _stream_ptr, _torch
+from .engine import _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
+from .table import kNoCompression
 
 # per-run status (include/lsbm_merge.h)
 MERGE_OK = 0
@@ -173,117 +174,40 @@ def cut_tables(block_first, block_bytes, max_file_size):
     return table_first, table_block_first
 
 
-def _get_varint64(buf, p):
-    v, shift = 0, 0
-    while True:
-        b = buf[p]
-        p += 1
-        v |= (b & 127) << shift
-        if b < 128:
-            return v, p
-        shift += 7
-
-
 def index_data_handles(image, index_handle):
     """The data block handles an index block lists (BlockHandle::DecodeFrom of
     every index value), as an int64 numpy array of {offset, size} pairs."""
-    from . import block
-    torch = _torch()
-    ih = torch.tensor([int(index_handle[0]), int(index_handle[1])], dtype=torch.int64, device=image.device)
-    _, _, values, _, st = block.decode(image, ih)
-    if int(st.cpu()[0]) != block.BLOCK_OK:
-        raise ValueError("index block: " + block.STATUS_MESSAGE.get(int(st.cpu()[0]), "bad"))
-    lo, hi = int(index_handle[0]), int(index_handle[0]) + int(index_handle[1])
-    buf = image[lo:hi].cpu().numpy().tobytes()
-    out = []
-    for off, _ in values.cpu().tolist():
-        o, p = _get_varint64(buf, off - lo)
-        s, _ = _get_varint64(buf, p)
-        out += [o, s]
-    return np.array(out, dtype=np.int64)
+    from . import sstable
+    return sstable._index_data_handles(image, index_handle, None, sstable._in_place)
 
 
 def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None, cmp=INTERNAL_KEY, drop=False,
             smallest_snapshot=None, bottom_level=False, block_size=4096, restart_interval=16, bits_per_key=None,
             stream=None):
     """The table-to-table part of DoCompactionWork for device-resident
-    kNoCompression tables (sstable.compact: either block type): images[t] is input table t's file image and
-    data_handles[t] its data blocks' {offset, size} pairs (or index_handles[t]
-    its index block's (offset, size), from which they are read).  Input t is
-    run t of the merge, so list the inputs as the reference's MergingIterator
-    has them: for equal keys the earlier table wins.
+    kNoCompression tables (sstable.compact: either block type): images[t] is
+    input table t's file image and data_handles[t] its data blocks' {offset,
+    size} pairs (or index_handles[t] its index block's (offset, size), from
+    which they are read).  Input t is run t of the merge, so list the inputs as
+    the reference's MergingIterator has them: for equal keys the earlier table
+    wins.
 
     On one stream: the images are concatenated into one value image, every
-    data block is scanned and decoded (block.scan / block.decode), the runs are
-    merged (merge), the output is planned as one table (block_build.plan), cut
-    into tables by max_file_size (cut_tables) and each table is written by
-    block_build.table_build.  No entry touches the host; the host reads counts
-    and block sizes.  Returns [OutputTable(image, data_handles, index_handle)]."""
+    data block is scanned and decoded where it lies (block.scan / block.decode:
+    no ReadBlock, no trailer is verified), the runs are merged (merge), the
+    output is planned as one table (block_build.plan) and its data blocks are
+    built, the blocks are cut into tables by max_file_size (cut_tables) and
+    sstable.finish_tables finishes every table in one chain.  This is
+    sstable.compact's body with another way to a block's contents.  No entry
+    touches the host; the host reads counts and block sizes.  Returns
+    [OutputTable(image, data_handles, index_handle)]; the images are views of
+    one arena, so holding one keeps the whole arena alive."""
     torch = _torch()
-    from . import block, block_build
+    from . import sstable
     if stream is not None:
         with torch.cuda.stream(stream):
             return compact(images, data_handles, max_file_size, index_handles, cmp, drop, smallest_snapshot,
                            bottom_level, block_size, restart_interval, bits_per_key)
-    if (data_handles is None) == (index_handles is None):
-        raise ValueError("give data_handles or index_handles")
-    if len(images) > MAX_RUNS:
-        raise ValueError(f"at most {MAX_RUNS} input tables")
-    if int(max_file_size) < 1:
-        raise ValueError("max_file_size must be at least 1")
-    _require_cuda(*images)
-    if not images:
-        return []
-    dev = images[0].device
-    if data_handles is None:
-        data_handles = [index_data_handles(img, ih) for img, ih in zip(images, index_handles)]
-    if len(data_handles) != len(images):
-        raise ValueError("one set of handles per image")
-    # 1. one value image; every handle moves by its image's place in it
-    image = torch.cat([img.reshape(-1) for img in images])
-    handles, blocks_before, base = [], [0], 0
-    for img, h in zip(images, data_handles):
-        h = torch.as_tensor(np.asarray(h.cpu() if hasattr(h, "cpu") else h, dtype=np.int64).reshape(-1, 2).copy())
-        h[:, 0] += base
-        handles.append(h)
-        blocks_before.append(blocks_before[-1] + h.shape[0])
-        base += img.numel()
-    handles = torch.cat(handles).reshape(-1).contiguous().to(dev)
-    # 2. the entries of every data block, one run per input table
-    counts, st = block.scan(image, handles)
-    _raise_on(st, "scan")
-    nb = counts.shape[0]
-    entry_base = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
-    key_base = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
-    if nb:
-        torch.cumsum(counts[:, 0], 0, out=entry_base[1:])
-        torch.cumsum(counts[:, 1], 0, out=key_base[1:])
-    keys, key_offsets, values, _, st = block.decode(image, handles, entry_base, key_base)
-    _raise_on(st, "decode")
-    run_first = entry_base[torch.tensor(blocks_before, dtype=torch.int64, device=dev)].contiguous()
-    # 3. the merge, the single-table plan of its output, the cut
-    m = merge(keys, key_offsets, values, run_first, cmp, drop, smallest_snapshot, bottom_level)
-    bad = [(r, int(s)) for r, s in enumerate(m.run_status.cpu().tolist()) if s != MERGE_OK]
-    if bad:
-        raise ValueError(f"input table {bad[0][0]}: {STATUS_MESSAGE.get(bad[0][1], bad[0][1])}")
-    n_out = m.key_offsets.numel() - 1
-    if n_out == 0:
-        return []
-    m_values = m.values.reshape(-1).contiguous()
-    p = block_build.plan(m.keys, m.key_offsets, m_values, torch.tensor([0, n_out], dtype=torch.int64, device=dev),
-                         block_size, restart_interval)
-    _raise_on(p.status, "plan")
-    n_blocks = int(p.table_block_first[-1])
-    table_first, _ = cut_tables(p.block_first[:n_blocks + 1].cpu().tolist(), p.block_bytes[:n_blocks].cpu().tolist(),
-                                int(max_file_size))
-    # 4. each output table's slice of the merged entries -> its file
-    out = []
-    key_at = m.key_offsets[torch.tensor(table_first, dtype=torch.int64, device=dev)].cpu().tolist()
-    for t in range(len(table_first) - 1):
-        e0, e1 = table_first[t], table_first[t + 1]
-        t_off = (m.key_offsets[e0:e1 + 1] - key_at[t]).contiguous()
-        t_keys = m.keys[key_at[t]:key_at[t + 1]].contiguous()
-        t_values = m_values[2 * e0:2 * e1].contiguous()
-        out.append(OutputTable(*block_build.table_build(t_keys, t_off, t_values, image, cmp, block_size,
-                                                        restart_interval, bits_per_key)))
-    return out
+    return sstable._compact(sstable._in_place, images, data_handles, max_file_size, index_handles, cmp, drop,
+                            smallest_snapshot, bottom_level, block_size, restart_interval, bits_per_key,
+                            kNoCompression, None)

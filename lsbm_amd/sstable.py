@@ -12,12 +12,6 @@ torch's current stream).
                                        every block, raw or compressed, moved to
                                        its final offset
     read_blocks(image, handles, ...)   batched ReadBlock (table/format.cc:66-148)
-    write_table(keys, key_offsets, values, value_image, ...)
-                                       TableBuilder with WriteBlock's rule on the
-                                       data, metaindex and index blocks
-    table_get(image, index_handle, keys, key_offsets, ...)
-                                       Table::InternalGet over either block type
-    compact(images, ...)               merge.compact over either block type
     pack_plan_tables, filter_layout, metaindex_blocks, place_tables
                                        include/lsbm_table_write.h: the pack plan
                                        restarting at every table, every table's
@@ -27,12 +21,22 @@ torch's current stream).
                                        TableBuilder from the first WriteBlock to
                                        the footer for many tables in one chain
     write_tables(keys, key_offsets, values, value_image, table_first, ...)
-                                       write_table for many tables at once; what
-                                       compact(batched=True) and
-                                       memtable.flush_many write through
+                                       TableBuilder with WriteBlock's rule on the
+                                       data, metaindex and index blocks, for many
+                                       tables at once: the one table writer
+    write_table(keys, key_offsets, values, value_image, ...)
+                                       write_tables of one table
+    table_get(image, index_handle, keys, key_offsets, ...)
+                                       Table::InternalGet over either block type
+    compact(images, ...)               merge.compact over either block type
 
-Handles are int64 {offset, size} pairs.  block.table_get, block_build.table_build
-and merge.compact keep their kNoCompression-only behaviour.
+Handles are int64 {offset, size} pairs.  Every table of the library is written
+by write_tables / finish_tables: block_build.table_build, memtable.flush and
+flush_many plan their entries through write_tables, and merge.compact and
+compact finish the blocks they have cut through finish_tables.  The tables of
+one call are views of one arena, so holding one image keeps the whole arena
+alive.  block.table_get, block_build.table_build and merge.compact keep their
+kNoCompression-only behaviour.
 """
 from collections import namedtuple
 
@@ -41,7 +45,7 @@ import numpy as np
 from ._lib import check, lib
 from .block import (BYTEWISE, GET_BAD_CHECKSUM, GET_BAD_TYPE, GET_FILTERED, INTERNAL_KEY, SEEK_BAD_HANDLE,
                     SEEK_VALID)
-from .engine import _ptr, _raise_on, _require_cuda, _stream_ptr, _torch
+from .engine import _buf, _check_tensors, _ptr, _raise_on, _require_cuda, _stream_ptr, _torch
 from .merge import OutputTable
 from .table import kBlockTrailerSize, kNoCompression, kSnappyCompression, seal_blocks
 
@@ -68,20 +72,12 @@ GET_BAD_COMPRESSED = 9    # the data block does not uncompress, or is READ_TOO_L
 COMP_NONE = -1            # comp_len of a block that could not be compressed (UINT64_MAX)
 
 GetResult = namedtuple("GetResult", "state key_len value data_handle value_image")
-# data blocks built (and compressed) once, for write_table's second half
+# data blocks built (and compressed) once, for finish_tables
 _Blocks = namedtuple("_Blocks", "raw raw_handles comp comp_offsets comp_len")
 
 
-def _i64(t, name):
-    torch = _torch()
-    if t.dtype != torch.int64 or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous int64 tensor")
-
-
-def _u8(t, name):
-    torch = _torch()
-    if t.dtype != torch.uint8 or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous uint8 tensor")
+def _check(**ts):
+    _check_tensors(ts, u8=("image", "raw", "comp", "types", "out", "arena", "filter", "keys"))
 
 
 def _scratch(n, dev):
@@ -105,12 +101,10 @@ def pack_plan(raw_len, comp_len=None, first_offset=0, gap=kBlockTrailerSize, str
     sizes and gaps before it, end = the offset after the last block's gap."""
     torch = _torch()
     _require_cuda(raw_len, comp_len)
-    _i64(raw_len, "raw_len")
+    _check(raw_len=raw_len, comp_len=comp_len)
     n = raw_len.numel()
-    if comp_len is not None:
-        _i64(comp_len, "comp_len")
-        if comp_len.numel() != n:
-            raise ValueError("comp_len needs one entry per block")
+    if comp_len is not None and comp_len.numel() != n:
+        raise ValueError("comp_len needs one entry per block")
     dev = raw_len.device
     types = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)[:n]
     handles = torch.zeros(max(2 * n, 1), dtype=torch.int64, device=dev)[:2 * n]
@@ -128,13 +122,8 @@ def pack(raw, raw_handles, comp, comp_offsets, types, handles, out, gap=kBlockTr
     comp_offsets may be None when no block is).  Returns status int32[n]."""
     torch = _torch()
     _require_cuda(raw, raw_handles, comp, comp_offsets, types, handles, out)
-    _u8(out, "out")
-    _u8(types, "types")
-    _i64(handles, "handles")
-    for t, name, chk in ((raw, "raw", _u8), (comp, "comp", _u8), (raw_handles, "raw_handles", _i64),
-                         (comp_offsets, "comp_offsets", _i64)):
-        if t is not None:
-            chk(t, name)
+    _check(out=out, types=types, handles=handles, raw=raw, comp=comp, raw_handles=raw_handles,
+           comp_offsets=comp_offsets)
     n = types.numel()
     if handles.numel() != 2 * n or (raw_handles is not None and raw_handles.numel() != 2 * n) or \
             (comp_offsets is not None and comp_offsets.numel() != n):
@@ -195,8 +184,7 @@ def read_blocks(image, handles, verify=True, max_bytes=1 << 30, stream=None):
         with torch.cuda.stream(stream):
             return read_blocks(image, handles, verify, max_bytes)
     _require_cuda(image, handles)
-    _u8(image, "image")
-    _i64(handles, "handles")
+    _check(image=image, handles=handles)
     if handles.numel() % 2:
         raise ValueError("handles must be {offset, size} pairs")
     n = handles.numel() // 2
@@ -268,168 +256,6 @@ def read_blocks(image, handles, verify=True, max_bytes=1 << 30, stream=None):
     return contents, out_handles, status.to(torch.int32)
 
 
-# ---------------------------------------------------------------- the writer
-
-
-def _offsets_of(sizes, dev):
-    """Host sizes -> (int64 n + 1 running sums on the device, their total)."""
-    torch = _torch()
-    offs = np.zeros(len(sizes) + 1, dtype=np.int64)
-    np.cumsum(np.asarray(sizes, dtype=np.int64), out=offs[1:])
-    return torch.from_numpy(offs).to(dev), int(offs[-1])
-
-
-def _compress(raw, offsets, sizes):
-    """snappy.compress of blocks that tile `raw` (host sizes): (comp, comp_offsets
-    int64[n], comp_len int64[n])."""
-    torch = _torch()
-    from . import snappy
-    caps = [32 + s + s // 6 for s in sizes]
-    out_offsets, total = _offsets_of(caps, raw.device)
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=raw.device)
-    _, _, clen = snappy.compress(raw, offsets, out, out_offsets)
-    return out, out_offsets[:-1].contiguous(), clen.contiguous()
-
-
-def _build_data_blocks(keys, key_offsets, values, value_image, block_first, sizes, restart_interval, compression):
-    """The data blocks built side by side into a staging image and, under
-    kSnappyCompression, compressed: _Blocks."""
-    torch = _torch()
-    from . import block_build
-    dev = keys.device
-    offsets, total = _offsets_of(sizes, dev)
-    raw = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)[:total]
-    raw_handles = torch.stack([offsets[:-1], offsets[1:] - offsets[:-1]], 1).reshape(-1).contiguous()
-    if len(sizes):
-        _, st = block_build.build(keys, key_offsets, values, value_image, block_first, raw, raw_handles,
-                                  restart_interval)
-        _raise_on(st, "build")
-    if compression == kSnappyCompression and len(sizes):
-        comp, comp_offsets, comp_len = _compress(raw, offsets, sizes)
-        return _Blocks(raw, raw_handles, comp, comp_offsets, comp_len)
-    return _Blocks(raw, raw_handles, None, None, None)
-
-
-def _finish_table(keys, key_offsets, block_first, blocks, cmp, restart_interval, bits_per_key, compression):
-    """TableBuilder from the first WriteBlock to the footer, over data blocks
-    that are already built (and compressed): block b = entries
-    [block_first[b], block_first[b+1]) of keys / key_offsets.  Returns
-    (image, data_handles, index_handle)."""
-    torch = _torch()
-    from . import block_build, bloom
-    dev = keys.device
-    n = key_offsets.numel() - 1
-    nb = block_first.numel() - 1
-    snappy_on = compression == kSnappyCompression
-    # 1. WriteBlock's rule over the data blocks; 2. the one read of their handles
-    raw_len = blocks.raw_handles.view(-1, 2)[:, 1].contiguous() if nb else \
-        torch.zeros(0, dtype=torch.int64, device=dev)
-    d_types, d_handles, d_end = pack_plan(raw_len, blocks.comp_len if snappy_on else None)
-    host = torch.cat([d_handles, d_end, block_first]).cpu().numpy()
-    data_handles, data_end, first_host = host[:2 * nb], int(host[2 * nb]), host[2 * nb + 1:]
-    # 3. the filter block: StartBlock sees the packed offsets
-    filt = None
-    if bits_per_key is not None:
-        starts = list(data_handles[0::2]) + ([data_end] if nb else [])
-        firsts = list(first_host) + ([n] if nb else [])
-        filt = bloom.build_filter_block(keys, key_offsets, starts, firsts, int(bits_per_key),
-                                        strip=8 if cmp == INTERNAL_KEY else 0)
-    # 4. the metaindex block and 5. the index block, raw, side by side in a staging image
-    if filt is not None:
-        meta_value = block_build.encode_handle(data_end, len(filt))
-        m_keys = torch.tensor(list(block_build.FILTER_KEY), dtype=torch.uint8, device=dev)
-        m_off = torch.tensor([0, len(block_build.FILTER_KEY)], dtype=torch.int64, device=dev)
-        m_values = torch.tensor([0, len(meta_value)], dtype=torch.int64, device=dev)
-        m_image = torch.tensor(list(meta_value), dtype=torch.uint8, device=dev)
-        m_first = torch.tensor([0, 1], dtype=torch.int64, device=dev)
-        meta_size = 3 + len(block_build.FILTER_KEY) + len(meta_value) + 8
-    else:
-        m_keys = torch.zeros(0, dtype=torch.uint8, device=dev)
-        m_off = torch.zeros(1, dtype=torch.int64, device=dev)
-        m_values = torch.zeros(0, dtype=torch.int64, device=dev)
-        m_image = torch.zeros(0, dtype=torch.uint8, device=dev)
-        m_first = torch.zeros(2, dtype=torch.int64, device=dev)
-        meta_size = 8
-    tbf = torch.tensor([0, nb], dtype=torch.int64, device=dev)
-    isize, ist = block_build.index_block(keys, key_offsets, block_first, tbf, d_handles, cmp)
-    _raise_on(ist, "index block")
-    index_size = int(isize[0])
-    filt_size = len(filt) if filt is not None else 0
-    tail_sizes = ([filt_size] if filt is not None else []) + [meta_size, index_size]
-    tail_offsets, tail_total = _offsets_of(tail_sizes, dev)
-    tail = torch.zeros(tail_total, dtype=torch.uint8, device=dev)
-    tail_raw_handles = torch.stack([tail_offsets[:-1], tail_offsets[1:] - tail_offsets[:-1]], 1).reshape(-1).contiguous()
-    if filt is not None:
-        tail[:filt_size] = torch.from_numpy(np.frombuffer(filt, dtype=np.uint8).copy()).to(dev)
-    _, st = block_build.build(m_keys, m_off, m_values, m_image, m_first, tail,
-                              tail_raw_handles[-4:-2].contiguous(), restart_interval)
-    _raise_on(st, "metaindex block")
-    _, st = block_build.index_block(keys, key_offsets, block_first, tbf, d_handles, cmp, tail,
-                                    tail_raw_handles[-2:].contiguous())
-    _raise_on(st, "index block")
-    tail_comp = tail_comp_offsets = tail_comp_len = None
-    if snappy_on:
-        tail_comp, tail_comp_offsets, tail_comp_len = _compress(tail, tail_offsets, tail_sizes)
-        if filt is not None:  # the filter block is WriteRawBlock(kNoCompression)
-            tail_comp_len = tail_comp_len.clone()
-            tail_comp_len[0] = COMP_NONE
-    tail_raw_len = torch.tensor(tail_sizes, dtype=torch.int64, device=dev)
-    t_types, t_handles, t_end = pack_plan(tail_raw_len, tail_comp_len, data_end)
-    t_host = torch.cat([t_handles, t_end]).cpu().numpy()
-    end = int(t_host[-1])
-    meta_handle = (int(t_host[-5]), int(t_host[-4]))
-    index_handle = (int(t_host[-3]), int(t_host[-2]))
-    # 6. everything to its place, every trailer, the footer
-    image = torch.zeros(end + block_build.kFooterEncodedLength, dtype=torch.uint8, device=dev)
-    if nb:
-        _raise_on(pack(blocks.raw, blocks.raw_handles, blocks.comp if snappy_on else None,
-                       blocks.comp_offsets if snappy_on else None, d_types, d_handles, image), "pack")
-    _raise_on(pack(tail, tail_raw_handles, tail_comp, tail_comp_offsets, t_types, t_handles, image), "pack")
-    seal_blocks(image, torch.cat([d_handles, t_handles]).contiguous(), torch.cat([d_types, t_types]).contiguous())
-    image[end:] = torch.tensor(list(block_build.footer(meta_handle, index_handle)), dtype=torch.uint8, device=dev)
-    return image, d_handles, index_handle
-
-
-def write_table(keys, key_offsets, values, value_image, cmp=INTERNAL_KEY, block_size=4096, restart_interval=16,
-                bits_per_key=None, compression=kSnappyCompression, stream=None):
-    """TableBuilder (table/table_builder.cc) Add for every entry, then Finish,
-    with WriteBlock's rule (the snappy form is kept where it is smaller than
-    raw - raw / 8) on the data blocks, the metaindex block and the index block;
-    the filter block is written raw.  The flush rule looks at the uncompressed
-    estimate, so the plan is block_build.plan's.  The data blocks are built
-    into a staging image, compressed and laid out by pack_plan; their packed
-    offsets feed the filter block and the index block; then every block is
-    moved to its place, sealed with its type, and the footer follows.  With
-    compression=kNoCompression the bytes are block_build.table_build's.
-    Returns (file_image uint8 device tensor, data_handles int64 device tensor
-    of {offset, size} pairs, index_handle (offset, size))."""
-    torch = _torch()
-    from . import block_build
-    if compression not in (kNoCompression, kSnappyCompression):
-        raise ValueError("unknown compression type")
-    if cmp not in (BYTEWISE, INTERNAL_KEY):
-        raise ValueError("unknown comparator")
-    if stream is not None:  # (the copies between the steps are torch's: on the same stream)
-        with torch.cuda.stream(stream):
-            return write_table(keys, key_offsets, values, value_image, cmp, block_size, restart_interval,
-                               bits_per_key, compression)
-    _require_cuda(keys, key_offsets, values, value_image)
-    dev = keys.device
-    n = key_offsets.numel() - 1
-    if n < 0 or values.numel() != 2 * n:
-        raise ValueError("values must be one {offset, length} pair per entry")
-    values = values.reshape(-1)
-    p = block_build.plan(keys, key_offsets, values, torch.tensor([0, n], dtype=torch.int64, device=dev),
-                         block_size, restart_interval)
-    _raise_on(p.status, "plan")
-    nb = int(p.table_block_first[-1])
-    sizes = p.block_bytes[:nb].cpu().tolist()
-    block_first = p.block_first[:nb + 1].contiguous()
-    blocks = _build_data_blocks(keys, key_offsets, values, value_image, block_first, sizes, restart_interval,
-                                compression)
-    return _finish_table(keys, key_offsets, block_first, blocks, cmp, restart_interval, bits_per_key, compression)
-
-
 # ---------------------------------------------------------------- many tables in one chain
 
 TABLE_ALIGN = 256         # finish_tables puts every table at a multiple of it
@@ -468,7 +294,7 @@ def _tw_scratch(n_blocks, n_tables, dev):
 
 
 def _n_tables(table_block_first):
-    _i64(table_block_first, "table_block_first")
+    _check(table_block_first=table_block_first)
     if table_block_first.numel() < 1:
         raise ValueError("table_block_first needs n_tables + 1 entries")
     return table_block_first.numel() - 1
@@ -481,14 +307,11 @@ def pack_plan_tables(raw_len, comp_len, table_block_first, first_offset=None, ga
     int64[T], status int32[T])."""
     torch = _torch()
     _require_cuda(raw_len, comp_len, table_block_first, first_offset, types, handles, end, status)
-    _i64(raw_len, "raw_len")
+    _check(raw_len=raw_len, comp_len=comp_len, first_offset=first_offset)
     n, nt, dev = raw_len.numel(), _n_tables(table_block_first), raw_len.device
     for t, name, count in ((comp_len, "comp_len", n), (first_offset, "first_offset", nt)):
-        if t is not None:
-            _i64(t, name)
-            if t.numel() != count:
-                raise ValueError(f"{name} needs {count} entries")
-    from .engine import _buf
+        if t is not None and t.numel() != count:
+            raise ValueError(f"{name} needs {count} entries")
     types = _buf(n, torch.uint8, dev) if types is None else types
     handles = _buf(2 * n, torch.int64, dev) if handles is None else handles
     end = _buf(nt, torch.int64, dev) if end is None else end
@@ -512,10 +335,8 @@ def filter_layout(block_first, table_block_first, data_handles, data_end, bits_p
     counts) filter_first / filter_out in bloom.build_filters' shape, and every
     table's trailer written into its window."""
     torch = _torch()
-    from .engine import _buf
     _require_cuda(block_first, table_block_first, data_handles, data_end, out, out_handles)
-    for t, name in ((block_first, "block_first"), (data_handles, "data_handles"), (data_end, "data_end")):
-        _i64(t, name)
+    _check(block_first=block_first, data_handles=data_handles, data_end=data_end, out=out, out_handles=out_handles)
     n, nt, dev = block_first.numel() - 1, _n_tables(table_block_first), block_first.device
     if n < 0 or data_handles.numel() != 2 * n or data_end.numel() != nt:
         raise ValueError("block_first[n + 1], data_handles[2n] and data_end[T] are needed")
@@ -524,8 +345,6 @@ def filter_layout(block_first, table_block_first, data_handles, data_end, bits_p
     size, count, status = _buf(nt, torch.int64, dev), _buf(nt, torch.int64, dev), _buf(nt, torch.int32, dev)
     first = out_f = None
     if out is not None:
-        _u8(out, "out")
-        _i64(out_handles, "out_handles")
         if out_handles.numel() != 2 * nt:
             raise ValueError("out_handles needs one pair per table")
         first, out_f = _buf(int(filters_cap) + 1, torch.int64, dev), _buf(int(filters_cap), torch.int64, dev)
@@ -543,18 +362,12 @@ def metaindex_blocks(data_end, filter_size=None, out=None, out_handles=None, str
     """One metaindex block per table (lsbm_metaindex_build_dev): (sizes
     int64[T], status int32[T]); with out / out_handles the bytes too."""
     torch = _torch()
-    from .engine import _buf
     _require_cuda(data_end, filter_size, out, out_handles)
-    _i64(data_end, "data_end")
+    _check(data_end=data_end, filter_size=filter_size, out=out, out_handles=out_handles)
     nt, dev = data_end.numel(), data_end.device
-    if filter_size is not None:
-        _i64(filter_size, "filter_size")
     if (filter_size is not None and filter_size.numel() != nt) or (out is None) != (out_handles is None) or \
             (out_handles is not None and out_handles.numel() != 2 * nt):
         raise ValueError("filter_size[T], and out with out_handles[2T], are needed")
-    if out is not None:
-        _u8(out, "out")
-        _i64(out_handles, "out_handles")
     sizes, status = _buf(nt, torch.int64, dev), _buf(nt, torch.int32, dev)
     check(lib().lsbm_metaindex_build_dev(_ptr(data_end), _ptr(filter_size), nt, _ptr(sizes), _ptr(out),
                                          out.numel() if out is not None else 0, _ptr(out_handles), _ptr(status),
@@ -568,12 +381,8 @@ def place_tables(data_handles, table_block_first, tail_handles, tail_per_table, 
     int64[T], data_handles, tail_handles with their table's base added, status
     int32[T]); every table's footer is written into `arena`."""
     torch = _torch()
-    from .engine import _buf
     _require_cuda(data_handles, table_block_first, tail_handles, tail_end, table_base, arena)
-    for t, name in ((data_handles, "data_handles"), (tail_handles, "tail_handles"), (tail_end, "tail_end"),
-                    (table_base, "table_base")):
-        _i64(t, name)
-    _u8(arena, "arena")
+    _check(data_handles=data_handles, tail_handles=tail_handles, tail_end=tail_end, table_base=table_base, arena=arena)
     nt, dev = _n_tables(table_block_first), arena.device
     n, k = data_handles.numel() // 2, int(tail_per_table)
     if data_handles.numel() % 2 or tail_handles.numel() != 2 * k * nt or tail_end.numel() != nt or \
@@ -736,13 +545,54 @@ def finish_tables(keys, key_offsets, block_first, table_block_first, blocks, cmp
                         {"table_handles": th, "index_handles": ih, "table_block_first": tbf_host})
 
 
+def _build_blocks(keys, key_offsets, values, value_image, p, restart_interval, compression, raise_on):
+    """The data blocks of a plan (block_build.plan's result `p`), built side by
+    side into a staging image and, under kSnappyCompression, compressed:
+    (block_first, _Blocks).  The sizes stay on the device (running sums,
+    snappy.compress's own bounds); the host reads the plan once (its status,
+    the number of blocks, their bytes) and the build's status once.  raise_on
+    (status, what) words a failure."""
+    torch = _torch()
+    from . import block_build, snappy
+    dev = keys.device
+    worst, nb, total = (int(x) for x in torch.cat([_worst(p.status) if p.status.numel() else
+                                                   torch.zeros(1, dtype=torch.int64, device=dev),
+                                                   p.table_block_first[-1:], p.block_bytes.sum().reshape(1)])
+                        .cpu().tolist())
+    if worst:
+        raise_on(p.status, "plan")
+    block_first = p.block_first[:nb + 1].contiguous()
+    sizes = p.block_bytes[:nb]
+    offsets = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+    if nb:
+        torch.cumsum(sizes, 0, out=offsets[1:])
+    raw = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)[:total]
+    raw_handles = torch.stack([offsets[:-1], sizes], 1).reshape(-1).contiguous()
+    blocks = _Blocks(raw, raw_handles, None, None, None)
+    if nb:
+        _, st = block_build.build(keys, key_offsets, values, value_image, block_first, raw, raw_handles,
+                                  restart_interval)
+        if int(_worst(st).cpu()[0]):
+            raise_on(st, "build")
+        if compression == kSnappyCompression:
+            comp, comp_offsets, comp_len = snappy.compress(raw, offsets)
+            blocks = _Blocks(raw, raw_handles, comp, comp_offsets[:-1].contiguous(), comp_len.contiguous())
+    return block_first, blocks
+
+
 def write_tables(keys, key_offsets, values, value_image, table_first, cmp=INTERNAL_KEY, block_size=4096,
                  restart_interval=16, bits_per_key=None, compression=kSnappyCompression, stream=None):
-    """write_table for many tables in one chain: table t = entries
-    [table_first[t], table_first[t + 1]) (an int64 device tensor or a list;
-    the tables tile the entries).  Plan, build and compress as write_table does
-    them, over all tables at once, then finish_tables.  A table without entries
-    is the file write_table writes for no entries.  Returns a TablesResult."""
+    """TableBuilder (table/table_builder.cc) Add for every entry, then Finish,
+    for many tables in one chain: table t = entries [table_first[t],
+    table_first[t + 1]) (an int64 device tensor or a list; the tables tile the
+    entries).  WriteBlock's rule (the snappy form is kept where it is smaller
+    than raw - raw / 8) holds on the data blocks, the metaindex block and the
+    index block; the filter block is written raw.  The flush rule looks at the
+    uncompressed estimate, so the plan is block_build.plan's.  The data blocks
+    of all tables are built into a staging image and compressed (_build_blocks),
+    then finish_tables lays them out, builds what follows them and moves
+    everything into one arena.  A table without entries is the file TableBuilder
+    writes when Finish follows no Add.  Returns a TablesResult."""
     torch = _torch()
     from . import block_build
     if compression not in (kNoCompression, kSnappyCompression):
@@ -763,32 +613,23 @@ def write_tables(keys, key_offsets, values, value_image, table_first, cmp=INTERN
         table_first = torch.tensor([int(x) for x in table_first], dtype=torch.int64, device=dev)
     _require_cuda(table_first)
     p = block_build.plan(keys, key_offsets, values, table_first, block_size, restart_interval)
-    # the one read of the plan: its status, the number of blocks, their bytes
-    worst, nb, total = (int(x) for x in torch.cat([_worst(p.status) if p.status.numel() else
-                                                   torch.zeros(1, dtype=torch.int64, device=dev),
-                                                   p.table_block_first[-1:], p.block_bytes.sum().reshape(1)])
-                        .cpu().tolist())
-    if worst:
-        block_build._raise_on(p.status, "plan")
-    block_first = p.block_first[:nb + 1].contiguous()
-    sizes = p.block_bytes[:nb]
-    offsets = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
-    if nb:
-        torch.cumsum(sizes, 0, out=offsets[1:])
-    raw = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)[:total]
-    raw_handles = torch.stack([offsets[:-1], sizes], 1).reshape(-1).contiguous()
-    blocks = _Blocks(raw, raw_handles, None, None, None)
-    if nb:
-        _, st = block_build.build(keys, key_offsets, values, value_image, block_first, raw, raw_handles,
-                                  restart_interval)
-        if int(_worst(st).cpu()[0]):
-            block_build._raise_on(st, "build")
-        if compression == kSnappyCompression:
-            from . import snappy
-            comp, comp_offsets, comp_len = snappy.compress(raw, offsets)
-            blocks = _Blocks(raw, raw_handles, comp, comp_offsets[:-1].contiguous(), comp_len.contiguous())
+    block_first, blocks = _build_blocks(keys, key_offsets, values, value_image, p, restart_interval, compression,
+                                        block_build._raise_on)
     return finish_tables(keys, key_offsets, block_first, p.table_block_first, blocks, cmp, restart_interval,
                          bits_per_key, compression)
+
+
+def write_table(keys, key_offsets, values, value_image, cmp=INTERNAL_KEY, block_size=4096, restart_interval=16,
+                bits_per_key=None, compression=kSnappyCompression, stream=None):
+    """write_tables of one table: (file_image uint8 device tensor, data_handles
+    int64 device tensor of {offset, size} pairs, index_handle (offset, size)).
+    The image is a view of write_tables' arena, contiguous and of the file's
+    size.  Every failure is write_tables': a plan or a build that fails raises
+    in block_build's words ("plan: block would reach 2^32 bytes")."""
+    _require_cuda(key_offsets)
+    res = write_tables(keys, key_offsets, values, value_image, [0, key_offsets.numel() - 1], cmp, block_size,
+                       restart_interval, bits_per_key, compression, stream)
+    return res.table(0), res.table_data_handles(0), res.index_handle(0)
 
 
 # ---------------------------------------------------------------- Get
@@ -827,9 +668,7 @@ def table_get(image, index_handle, keys, key_offsets, filter=None, verify=True, 
             return table_get(image, index_handle, keys, key_offsets, filter, verify, cmp, bits_per_key,
                              bloom_bits_use, max_bytes)
     _require_cuda(image, keys, key_offsets, filter)
-    _u8(image, "image")
-    _u8(keys, "keys")
-    _i64(key_offsets, "key_offsets")
+    _check(image=image, keys=keys, key_offsets=key_offsets, filter=filter)
     n = key_offsets.numel() - 1
     dev = image.device
     ih = torch.tensor([int(index_handle[0]), int(index_handle[1])], dtype=torch.int64, device=dev)
@@ -843,7 +682,6 @@ def table_get(image, index_handle, keys, key_offsets, filter=None, verify=True, 
     found = state == SEEK_VALID
     handle = torch.where(found[:, None], idx.handle, torch.zeros_like(idx.handle))
     if filter is not None:  # 2. filter->KeyMayMatch(handle.offset(), k)
-        _u8(filter, "filter")
         fh = torch.tensor([0, filter.numel()], dtype=torch.int64, device=dev).repeat(n)
         may, _ = bloom.filter_block_may_match(filter, fh, handle[:, 0].contiguous(), keys, key_offsets,
                                               bits_per_key, bloom_bits_use,
@@ -873,48 +711,56 @@ def table_get(image, index_handle, keys, key_offsets, filter=None, verify=True, 
 # ---------------------------------------------------------------- compaction
 
 
-def index_data_handles(image, index_handle, verify=True):
-    """The data block handles an index block of either type lists, as an int64
-    numpy array of {offset, size} pairs."""
+def _in_place(image, handles, verify=None):
+    """read_blocks' shape for blocks taken as they lie in the image, which is how
+    merge.compact reads its kNoCompression inputs: no ReadBlock, no status."""
+    return image, handles, None
+
+
+def _get_varint64(buf, p):
+    v, shift = 0, 0
+    while True:
+        b = buf[p]
+        p += 1
+        v |= (b & 127) << shift
+        if b < 128:
+            return v, p
+        shift += 7
+
+
+def _index_data_handles(image, index_handle, verify, read):
+    """BlockHandle::DecodeFrom of every value of an index block whose contents
+    `read` (read_blocks or _in_place) gives: int64 numpy {offset, size} pairs."""
     torch = _torch()
     from . import block
-    from .merge import _get_varint64
     ih = torch.tensor([int(index_handle[0]), int(index_handle[1])], dtype=torch.int64, device=image.device)
-    contents, oh, st = read_blocks(image, ih, verify)
-    if int(st.cpu()[0]) != READ_OK:
+    contents, oh, st = read(image, ih, verify)
+    if st is not None and int(st.cpu()[0]) != READ_OK:
         raise ValueError("index block: " + READ_MESSAGE[int(st.cpu()[0])])
     _, _, values, _, dst = block.decode(contents, oh)
     if int(dst.cpu()[0]) != block.BLOCK_OK:
         raise ValueError("index block: " + block.STATUS_MESSAGE.get(int(dst.cpu()[0]), "bad"))
-    buf = contents.cpu().numpy().tobytes()
+    lo, size = oh.cpu().tolist()
+    buf = contents[lo:lo + size].cpu().numpy().tobytes()
     out = []
     for off, _ in values.cpu().tolist():
-        o, p = _get_varint64(buf, off)
-        s, _ = _get_varint64(buf, p)
-        out += [o, s]
+        o, p = _get_varint64(buf, off - lo)
+        out += [o, _get_varint64(buf, p)[0]]
     return np.array(out, dtype=np.int64)
 
 
-def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None, cmp=INTERNAL_KEY, drop=False,
-            smallest_snapshot=None, bottom_level=False, block_size=4096, restart_interval=16, bits_per_key=None,
-            compression=kNoCompression, verify=True, stream=None, batched=False):
-    """merge.compact for tables whose blocks are of either type, with output
-    tables written under `compression`.  Every input data block goes through
-    read_blocks, whose contents are the value image that decode, merge and the
-    builder point into.  The merged entries are planned as one table; every
-    data block of that plan is built and compressed once; the cut
-    (merge.cut_tables) sees each block's packed size, as FileSize() does; and
-    each output table is finished from its slice of those blocks.  Returns
-    [OutputTable(image, data_handles, index_handle)].  batched=True finishes
-    every output table in one chain (finish_tables): the images are views of
-    one arena and their bytes are the same."""
+def index_data_handles(image, index_handle, verify=True):
+    """The data block handles an index block of either type lists, as an int64
+    numpy array of {offset, size} pairs."""
+    return _index_data_handles(image, index_handle, verify, read_blocks)
+
+
+def _compact(read, images, data_handles, max_file_size, index_handles, cmp, drop, smallest_snapshot, bottom_level,
+             block_size, restart_interval, bits_per_key, compression, verify):
+    """The one body of merge.compact (read = _in_place) and compact (read =
+    read_blocks), on torch's current stream."""
     torch = _torch()
     from . import block, block_build, merge
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return compact(images, data_handles, max_file_size, index_handles, cmp, drop, smallest_snapshot,
-                           bottom_level, block_size, restart_interval, bits_per_key, compression, verify, None,
-                           batched)
     if (data_handles is None) == (index_handles is None):
         raise ValueError("give data_handles or index_handles")
     if compression not in (kNoCompression, kSnappyCompression):
@@ -928,7 +774,7 @@ def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None
         return []
     dev = images[0].device
     if data_handles is None:
-        data_handles = [index_data_handles(img, ih, verify) for img, ih in zip(images, index_handles)]
+        data_handles = [_index_data_handles(img, ih, verify, read) for img, ih in zip(images, index_handles)]
     if len(data_handles) != len(images):
         raise ValueError("one set of handles per image")
     # 1. one file image; every handle moves by its image's place in it
@@ -941,13 +787,14 @@ def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None
         blocks_before.append(blocks_before[-1] + h.shape[0])
         base += img.numel()
     handles = torch.cat(handles).reshape(-1).contiguous().to(dev)
-    # 2. ReadBlock of every data block; the entries, one run per input table
-    contents, handles, st = read_blocks(image, handles, verify)
-    bad = [(b, int(s)) for b, s in enumerate(st.cpu().tolist()) if s != READ_OK]
-    if bad:
-        raise ValueError(f"input data block {bad[0][0]}: {READ_MESSAGE[bad[0][1]]}")
-    if contents.numel() == 0:
-        return []
+    # 2. every data block's contents (the value image from here on); the entries, one run per input table
+    contents, handles, st = read(image, handles, verify)
+    if st is not None:
+        bad = [(b, int(s)) for b, s in enumerate(st.cpu().tolist()) if s != READ_OK]
+        if bad:
+            raise ValueError(f"input data block {bad[0][0]}: {READ_MESSAGE[bad[0][1]]}")
+        if contents.numel() == 0:
+            return []
     counts, st = block.scan(contents, handles)
     _raise_on(st, "scan")
     nb = counts.shape[0]
@@ -970,34 +817,37 @@ def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None
     m_values = m.values.reshape(-1).contiguous()
     p = block_build.plan(m.keys, m.key_offsets, m_values, torch.tensor([0, n_out], dtype=torch.int64, device=dev),
                          block_size, restart_interval)
-    _raise_on(p.status, "plan")
-    n_blocks = int(p.table_block_first[-1])
-    block_first = p.block_first[:n_blocks + 1].contiguous()
-    first_host = block_first.cpu().tolist()
-    sizes = p.block_bytes[:n_blocks].cpu().tolist()
-    # 4. every data block once: built, compressed, ruled; the cut over the packed sizes
-    blocks = _build_data_blocks(m.keys, m.key_offsets, m_values, contents, block_first, sizes, restart_interval,
-                                compression)
+    # 4. every data block once: built, compressed, ruled; the cut over the packed sizes (one read)
+    block_first, blocks = _build_blocks(m.keys, m.key_offsets, m_values, contents, p, restart_interval, compression,
+                                        _raise_on)
+    n_blocks = block_first.numel() - 1
     _, packed, _ = pack_plan(blocks.raw_handles.view(-1, 2)[:, 1].contiguous(), blocks.comp_len)
-    table_first, table_block_first = merge.cut_tables(first_host, packed.view(-1, 2)[:, 1].cpu().tolist(),
-                                                      int(max_file_size))
-    if batched:  # 5. every output table in one chain
-        res = finish_tables(m.keys, m.key_offsets, block_first,
-                            torch.tensor(table_block_first, dtype=torch.int64, device=dev), blocks, cmp,
-                            restart_interval, bits_per_key, compression)
-        return [OutputTable(res.table(t), res.table_data_handles(t), res.index_handle(t))
-                for t in range(len(table_first) - 1)]
-    # 5. each output table from its slice of the entries and of the blocks
-    out = []
-    key_at = m.key_offsets[torch.tensor(table_first, dtype=torch.int64, device=dev)].cpu().tolist()
-    for t in range(len(table_first) - 1):
-        e0, e1 = table_first[t], table_first[t + 1]
-        b0, b1 = table_block_first[t], table_block_first[t + 1]
-        t_off = (m.key_offsets[e0:e1 + 1] - key_at[t]).contiguous()
-        t_keys = m.keys[key_at[t]:key_at[t + 1]].contiguous()
-        t_blocks = _Blocks(blocks.raw, blocks.raw_handles[2 * b0:2 * b1].contiguous(), blocks.comp,
-                           blocks.comp_offsets[b0:b1].contiguous() if blocks.comp is not None else None,
-                           blocks.comp_len[b0:b1].contiguous() if blocks.comp is not None else None)
-        out.append(OutputTable(*_finish_table(t_keys, t_off, (block_first[b0:b1 + 1] - e0).contiguous(), t_blocks,
-                                              cmp, restart_interval, bits_per_key, compression)))
-    return out
+    host = torch.cat([block_first, packed.view(-1, 2)[:, 1]]).cpu().tolist()
+    table_first, table_block_first = merge.cut_tables(host[:n_blocks + 1], host[n_blocks + 1:], int(max_file_size))
+    # 5. every output table in one chain
+    res = finish_tables(m.keys, m.key_offsets, block_first,
+                        torch.tensor(table_block_first, dtype=torch.int64, device=dev), blocks, cmp, restart_interval,
+                        bits_per_key, compression)
+    return [OutputTable(res.table(t), res.table_data_handles(t), res.index_handle(t))
+            for t in range(len(table_first) - 1)]
+
+
+def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None, cmp=INTERNAL_KEY, drop=False,
+            smallest_snapshot=None, bottom_level=False, block_size=4096, restart_interval=16, bits_per_key=None,
+            compression=kNoCompression, verify=True, stream=None):
+    """merge.compact for tables whose blocks are of either type, with output
+    tables written under `compression`.  Every input data block goes through
+    read_blocks, whose contents are the value image that decode, merge and the
+    builder point into.  The merged entries are planned as one table; every
+    data block of that plan is built and compressed once; the cut
+    (merge.cut_tables) sees each block's packed size, as FileSize() does; and
+    finish_tables finishes every output table from its slice of those blocks in
+    one chain.  Returns [OutputTable(image, data_handles, index_handle)]; the
+    images are views of one arena, so holding one keeps the whole arena alive."""
+    torch = _torch()
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return compact(images, data_handles, max_file_size, index_handles, cmp, drop, smallest_snapshot,
+                           bottom_level, block_size, restart_interval, bits_per_key, compression, verify)
+    return _compact(read_blocks, images, data_handles, max_file_size, index_handles, cmp, drop, smallest_snapshot,
+                    bottom_level, block_size, restart_interval, bits_per_key, compression, verify)

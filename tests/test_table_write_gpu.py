@@ -1,7 +1,7 @@
 """GPU tests of the batched table finish (include/lsbm_table_write.h;
 sstable.finish_tables / write_tables, memtable.sort_segments / flush_many, and
-the batched forms of sstable.compact and memtable.recover_all) against the
-reference-written fixtures, the models and the per-table paths.
+sstable.compact and memtable.recover_all, which write through them) against
+the reference-written fixtures, the host models and the one-table calls.
 """
 import random
 
@@ -104,10 +104,14 @@ def varied_tables(n_tables):
 
 
 @pytest.mark.parametrize("n_tables", [1, 2, 65])
-def test_write_tables_equals_write_table_of_each_slice(torch_cuda, n_tables):
+def test_write_tables_equals_write_table_of_each_slice(torch_cuda, n_tables, codec):  # noqa: F811
+    """A table's bytes do not depend on its neighbours (write_table is
+    write_tables of one table), and they are the host models'."""
     from lsbm_amd import sstable
     torch = torch_cuda
     tables = varied_tables(max(n_tables, 6))[:n_tables] if n_tables > 2 else varied_tables(6)[2 * n_tables:3 * n_tables]
+    if n_tables > 2:  # the smallest shapes stay in
+        assert tables[0] == [(b"only-key", b"value")] and tables[1] == []
     for bits_per_key in (None, 10):
         for compression in (0, 1):
             res = gpu_write_tables(torch, tables, (bm.BYTEWISE, 128, 4, bits_per_key), compression)
@@ -117,8 +121,13 @@ def test_write_tables_equals_write_table_of_each_slice(torch_cuda, n_tables):
                 image, handles, index_handle = sstable.write_table(E.keys, E.koff, E.values, E.image, bm.BYTEWISE, 128,
                                                                    4, bits_per_key, compression)
                 got = table_of(res, t)
+                assert image.is_contiguous() and image.numel() == len(got[0])
                 assert got[0] == tobytes(image), (n_tables, bits_per_key, compression, t)
                 assert got[1] == handles.cpu().numpy().reshape(-1, 2).tolist() and got[2] == list(index_handle)
+                want = stm.table_file(entries, bm.BYTEWISE, 128, 4, bits_per_key, codec[0]) if compression else \
+                    bd.table_file(entries, bm.BYTEWISE, 128, 4, bits_per_key)
+                assert got[0] == want[0], (n_tables, bits_per_key, compression, t)
+                assert got[1] == [list(h) for h in want[1]] and got[2] == list(want[2])
     if n_tables == 65:  # (the last call: bloom and snappy) data ends either side of 16,384, index blocks of both types
         last = [res.table_data_handles(t).cpu().tolist()[-2:] for t in (2, 3)]
         assert last[0][0] + last[0][1] + 5 < 16384 < last[1][0] + last[1][1] + 5
@@ -138,19 +147,33 @@ def test_host_reads_do_not_grow_with_the_tables(torch_cuda, monkeypatch):
             return real(self, *a, **kw)
         return call
 
-    reads = []
-    for n_tables in (2, 33):
-        tables = [tc._blocks_of_kinds("rxr"[:1 + t % 3], 128, 4, 100 + t) for t in range(n_tables)]
-        E, first = join(torch, tables)
-        first = _dev(torch, first)
-        from lsbm_amd import sstable
+    from lsbm_amd import memtable, sstable
+
+    def reads_of(call):
         with monkeypatch.context() as m:
             counts.clear()
             for name in ("cpu", "item", "tolist"):
                 m.setattr(torch.Tensor, name, counted(name))
-            sstable.write_tables(E.keys, E.koff, E.values, E.image, first, bm.BYTEWISE, 128, 4, 10, 1)
-            reads.append(dict(counts))
-    assert reads[0] == reads[1] and sum(reads[0].values()) > 0, reads
+            got = call()
+            return dict(counts), got
+
+    reads = []
+    for n_tables in (1, 2, 33):
+        tables = [tc._blocks_of_kinds("rxr"[:1 + t % 3], 128, 4, 100 + t) for t in range(n_tables)]
+        E, first = join(torch, tables)
+        first = _dev(torch, first)
+        reads.append(reads_of(lambda: sstable.write_tables(E.keys, E.koff, E.values, E.image, first, bm.BYTEWISE, 128,
+                                                           4, 10, 1))[0])
+    assert reads[0] == reads[1] == reads[2] and sum(reads[0].values()) > 0, reads
+    # recover_all: one log (no record of it is in error) cut into one, a few and many memtables
+    log = log_of(torch, dict(cases.scenarios())["five_memtables"])
+    reads, tables = [], []
+    for write_buffer_size in (1 << 30, 160 << 10, 64 << 10):
+        r, got = reads_of(lambda: memtable.recover_all(log, write_buffer_size=write_buffer_size, bits_per_key=10))
+        reads.append(r)
+        tables.append(len(got.flushes))
+    assert tables[0] == 1 < tables[1] < tables[2] >= 5, tables
+    assert reads[0] == reads[1] == reads[2] and sum(reads[0].values()) > 0, reads
 
 
 # ---------------------------------------------------------------- the filter layout
@@ -216,9 +239,9 @@ def test_filter_layout_single_and_second_of_three(torch_cuda, name):
 # ---------------------------------------------------------------- compaction
 
 
-def test_compact_batched_equals_the_fixture_and_the_loop(torch_cuda, fx):  # noqa: F811
+def test_compact_batched_equals_the_fixture_and_the_loop(torch_cuda, fx, codec):  # noqa: F811
     torch = torch_cuda
-    from lsbm_amd import sstable
+    from lsbm_amd import merge, sstable
     _, comp = fx
     c = dict(tc.COMPACTION)
     cmp, max_file_size = c.pop("cmp"), c.pop("max_file_size")
@@ -226,18 +249,26 @@ def test_compact_batched_equals_the_fixture_and_the_loop(torch_cuda, fx):  # noq
     handles = [np.array(r["data_handles"], dtype=np.int64).reshape(-1) for r in comp["inputs"]]
     want = [r["data"] for r in comp["outputs"]]
     assert len(want) >= 3
-    out = sstable.compact(images, handles, max_file_size, cmp=cmp, compression=1, batched=True, **c)
+    out = sstable.compact(images, handles, max_file_size, cmp=cmp, compression=1, **c)
     assert [tobytes(o.image) for o in out] == want
-    loop = sstable.compact(images, handles, max_file_size, cmp=cmp, compression=1, **c)
-    assert [o.data_handles.cpu().tolist() for o in out] == [o.data_handles.cpu().tolist() for o in loop]
-    assert [list(o.index_handle) for o in out] == [list(o.index_handle) for o in loop]
+    read = [stm.read_table(f, codec[1]) for f in want]  # (the handles the reference-written files hold)
+    assert [o.data_handles.cpu().numpy().reshape(-1, 2).tolist() for o in out] == \
+        [[list(h) for h in r["data_handles"]] for r in read]
+    assert [list(o.index_handle) for o in out] == [list(r["index_handle"]) for r in read]
     out = sstable.compact(images, None, max_file_size, index_handles=[r["index_handle"] for r in comp["inputs"]],
-                          cmp=cmp, compression=1, batched=True, **c)
+                          cmp=cmp, compression=1, **c)
     assert [tobytes(o.image) for o in out] == want
-    loop = sstable.compact(images, handles, max_file_size, cmp=cmp, compression=0, **c)
-    raw = sstable.compact(images, handles, max_file_size, cmp=cmp, compression=0, batched=True, **c)
-    assert [tobytes(o.image) for o in raw] == [tobytes(o.image) for o in loop] and len(raw) == len(loop) >= 3
-    assert [list(o.index_handle) for o in raw] == [list(o.index_handle) for o in loop]
+    # compression=0: the model merge of the inputs, cut over the raw block sizes, each table the host model's file
+    kept, _ = mm.merge_entries(tc.compaction_runs(), cmp, c["drop"], c["smallest_snapshot"], c["bottom_level"])
+    first, sizes = bd.plan([(k, len(v)) for k, v in kept], c["block_size"], c["restart_interval"])
+    table_first, _ = merge.cut_tables(first, sizes, max_file_size)
+    model = [bd.table_file(kept[e0:e1], cmp, c["block_size"], c["restart_interval"], c["bits_per_key"])
+             for e0, e1 in zip(table_first[:-1], table_first[1:])]
+    raw = sstable.compact(images, handles, max_file_size, cmp=cmp, compression=0, **c)
+    assert [tobytes(o.image) for o in raw] == [m[0] for m in model] and len(raw) >= 3
+    assert [o.data_handles.cpu().numpy().reshape(-1, 2).tolist() for o in raw] == \
+        [[list(h) for h in m[1]] for m in model]
+    assert [list(o.index_handle) for o in raw] == [list(m[2]) for m in model]
 
 
 # ---------------------------------------------------------------- the segmented sort
@@ -363,16 +394,35 @@ def test_flush_many_equals_flush_of_each_slice(torch_cuda):
         done += 1
         kw = dict(block_size=c["block_size"], restart_interval=c["restart_interval"], bits_per_key=c["bits_per_key"])
         splits = [[0, n], [0, n // 2, n], [0, 1, n // 3, n // 2, n - 1, n], [0, 0, n // 2, n // 2, n, n]]
+        host, pairs = tobytes(image), records.cpu().numpy().reshape(-1, 2).tolist()
+        model = {}  # (lo, hi) -> the host model's file of that memtable (None without entries)
         for mem_first in splits:
+            slices = list(zip(mem_first[:-1], mem_first[1:]))
+            for s in slices:
+                if s not in model:
+                    model[s] = mt.table_file(mt.entries(host, pairs[s[0]:s[1]])[0], c["block_size"],
+                                             c["restart_interval"], c["bits_per_key"])
             for compression in (0, 1):
                 got = memtable.flush_many(image, records, mem_first, compression=compression, **kw)
                 want = [memtable.flush(image, records[2 * lo:2 * hi].contiguous(), compression=compression, **kw)
-                        for lo, hi in zip(mem_first[:-1], mem_first[1:])]
+                        for lo, hi in slices]
                 want = [w for w in want if w.image is not None]
                 assert len(got) == len(want) >= 1, (c["name"], mem_first)
                 for f, t in zip(got, want):
                     same_flush(f, t, (c["name"], mem_first, compression))
+                if compression == 0:
+                    assert [tobytes(f.image) for f in got] == [model[s] for s in slices if model[s] is not None], \
+                        (c["name"], mem_first)
     assert done
+
+
+def flushes_of(image, bounds, **kw):
+    """memtable.flush of each slice [lo, hi) of log.read_records' records; memtables without entries are dropped."""
+    from lsbm_amd import log as lg
+    from lsbm_amd import memtable
+    r = lg.read_records(image)
+    out = [memtable.flush(r.image, r.records[lo:hi].reshape(-1).contiguous(), **kw) for lo, hi in bounds]
+    return [f for f in out if f.image is not None], r
 
 
 @pytest.mark.parametrize("name", ["five_memtables", "too_small", "records_in_error", "cut_on_last"])
@@ -380,12 +430,13 @@ def test_recover_all_batched_equals_the_loop(torch_cuda, name):
     from lsbm_amd import memtable
     reps = dict(cases.scenarios())[name]
     log = log_of(torch_cuda, reps)
-    want = memtable.recover_all(log, write_buffer_size=65536, bits_per_key=10)
-    got = memtable.recover_all(log, write_buffer_size=65536, bits_per_key=10, batched=True)
-    assert got.mem_first == want.mem_first and got.status == want.status
-    assert got.events.cpu().tolist() == want.events.cpu().tolist()
-    assert len(got.flushes) == len(want.flushes)
-    for f, t in zip(got.flushes, want.flushes):
+    got = memtable.recover_all(log, write_buffer_size=65536, bits_per_key=10)
+    mem_first = FIXTURE["scenarios"][name]["cuts"]["recover_65536"]["mem_first"] + [len(reps)]
+    want, r = flushes_of(log, zip(mem_first[:-1], mem_first[1:]), bits_per_key=10)
+    assert got.mem_first == mem_first and got.status is None
+    assert got.events.cpu().tolist() == r.events.cpu().tolist()
+    assert len(got.flushes) == len(want)
+    for f, t in zip(got.flushes, want):
         same_flush(f, t, name)
 
 
@@ -399,13 +450,25 @@ def test_recover_all_batched_paranoid_keeps_the_finished_tables_only(torch_cuda)
     torn = log.clone()
     torn[40000] ^= 0xFF
     for image in (log, torn):
-        want = memtable.recover_all(image, write_buffer_size=65536, paranoid=True)
-        got = memtable.recover_all(image, write_buffer_size=65536, paranoid=True, batched=True)
-        assert got.status == want.status and got.status.startswith("Corruption: ")
-        assert got.mem_first == want.mem_first and len(got.flushes) == len(want.flushes)
-        for f, t in zip(got.flushes, want.flushes):
+        loose = memtable.recover_all(image, write_buffer_size=65536)
+        got = memtable.recover_all(image, write_buffer_size=65536, paranoid=True)
+        assert got.status.startswith("Corruption: ")
+        # the records the loop took: up to the reader's first report, or to the first record in error
+        taken = min([bad] + ([int(got.events[0][0])] if got.events.shape[0] else []))
+        if image is log:
+            assert got.status == "Corruption: " + memtable.STATUS_MESSAGE[s["status"][bad]]
+        assert got.events.cpu().tolist() == loose.events.cpu().tolist()
+        # the cut runs record by record: the cuts of a prefix are a prefix of the cuts
+        k = len(got.mem_first) - 1
+        assert got.mem_first == loose.mem_first[:k] + [taken] and 0 < taken < loose.mem_first[-1]
+        # the memtables the whole log closes too are written, the one in progress is not
+        closed = set(zip(loose.mem_first[:-2], loose.mem_first[1:-1]))
+        bounds = [b for b in zip(got.mem_first[:-1], got.mem_first[1:]) if b in closed]
+        want, _ = flushes_of(image, bounds)
+        assert len(want) == len(got.flushes) and (image is torn or len(want) >= 1)
+        for f, t in zip(got.flushes, want):
             same_flush(f, t, "paranoid")
-    loose = memtable.recover_all(log, write_buffer_size=65536, batched=True)
+    loose = memtable.recover_all(log, write_buffer_size=65536)
     assert 1 <= len([m for m in range(len(loose.mem_first) - 1) if loose.mem_first[m + 1] <= bad]) < len(loose.flushes)
 
 
