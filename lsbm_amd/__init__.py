@@ -24,13 +24,17 @@
                     SeekToLast / Next / Prev / status for many range queries at once (Version.view)
   lsbm_amd.write    batched DB::Write: WriteBatch::Put / Delete encoding, BuildBatchGroup's rule, the
                     groups' reps and sequence numbers, log::Writer::AddRecord's framing (write_batches)
+  lsbm_amd.manifest MANIFEST snapshots: batched VersionEdit::DecodeFrom / EncodeTo, the entries of one
+                    long record found in parallel, WriteSnapshot's record from a device-resident file
+                    table (snapshot, manifest_image), BasicVersionSet::Recover's loop (recover)
 
 The compute lives in lsbm_amd/liblsbm_crc32c.so (hand-written gfx950 HIP
 kernels behind the C ABIs in include/lsbm_crc32c.h, include/lsbm_bloom.h, include/lsbm_snappy.h and
 include/lsbm_block.h, include/lsbm_block_build.h, include/lsbm_merge.h, include/lsbm_table_pack.h,
-include/lsbm_memtable.h, include/lsbm_get.h, include/lsbm_iter.h, include/lsbm_write.h, include/lsbm_log_read.h).
+include/lsbm_memtable.h, include/lsbm_get.h, include/lsbm_iter.h, include/lsbm_write.h, include/lsbm_log_read.h,
+include/lsbm_manifest.h).
 """
 from ._lib import LIB_PATH, LsbmError, lib  # noqa: F401
 
 __all__ = ["LIB_PATH", "LsbmError", "lib", "crc32c", "engine", "table", "log", "bloom", "snappy",
-           "block", "block_build", "merge", "sstable", "memtable", "db", "scan", "write"]
+           "block", "block_build", "merge", "sstable", "memtable", "db", "scan", "write", "manifest"]

@@ -207,6 +207,19 @@ TABLE_WRITE_SIGNATURES = {
     "lsbm_memtable_sort_segments_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
 }
 
+# every symbol include/lsbm_manifest.h declares
+_ENCODE_INPUTS = [_vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64]
+MANIFEST_SIGNATURES = {
+    "lsbm_edit_decode_scratch_bytes": (_u64, [_u64, _u64]),
+    "lsbm_edit_encode_scratch_bytes": (_u64, [_u64, _u64, _u64]),
+    "lsbm_edit_decode_plan_dev": (_int, [_vp, _u64, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64,
+                                         _vp]),
+    "lsbm_edit_decode_emit_dev": (_int, [_vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp,
+                                         _u64, _vp]),
+    "lsbm_edit_encode_plan_dev": (_int, _ENCODE_INPUTS + [_u64, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "lsbm_edit_encode_emit_dev": (_int, _ENCODE_INPUTS + [_vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp]),
+}
+
 _lib = None
 
 
@@ -231,7 +244,8 @@ def lib():
                                   + list(TABLE_PACK_SIGNATURES.items()) + list(MEMTABLE_SIGNATURES.items())
                                   + list(GET_SIGNATURES.items()) + list(ITER_SIGNATURES.items())
                                   + list(WRITE_SIGNATURES.items()) + list(LOG_READ_SIGNATURES.items())
-                                  + list(MEMCUT_SIGNATURES.items()) + list(TABLE_WRITE_SIGNATURES.items())):
+                                  + list(MEMCUT_SIGNATURES.items()) + list(TABLE_WRITE_SIGNATURES.items())
+                                  + list(MANIFEST_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)
