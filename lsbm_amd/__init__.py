@@ -27,14 +27,17 @@
   lsbm_amd.manifest MANIFEST snapshots: batched VersionEdit::DecodeFrom / EncodeTo, the entries of one
                     long record found in parallel, WriteSnapshot's record from a device-resident file
                     table (snapshot, manifest_image), BasicVersionSet::Recover's loop (recover)
+  lsbm_amd.buffered LSbM's buffered Get: Builder::SaveTo's sorted-table lists, the slots Version::Get can reach,
+                    the probe plan under covered_by_del / covered_by_ins / covered_by_head / checkwb, and
+                    table reads by probe rank (BufferedVersion.get, from_manifest)
 
 The compute lives in lsbm_amd/liblsbm_crc32c.so (hand-written gfx950 HIP
 kernels behind the C ABIs in include/lsbm_crc32c.h, include/lsbm_bloom.h, include/lsbm_snappy.h and
 include/lsbm_block.h, include/lsbm_block_build.h, include/lsbm_merge.h, include/lsbm_table_pack.h,
 include/lsbm_memtable.h, include/lsbm_get.h, include/lsbm_iter.h, include/lsbm_write.h, include/lsbm_log_read.h,
-include/lsbm_manifest.h).
+include/lsbm_manifest.h, include/lsbm_probe.h).
 """
 from ._lib import LIB_PATH, LsbmError, lib  # noqa: F401
 
 __all__ = ["LIB_PATH", "LsbmError", "lib", "crc32c", "engine", "table", "log", "bloom", "snappy",
-           "block", "block_build", "merge", "sstable", "memtable", "db", "scan", "write", "manifest"]
+           "block", "block_build", "merge", "sstable", "memtable", "db", "scan", "write", "manifest", "buffered"]

@@ -220,6 +220,13 @@ MANIFEST_SIGNATURES = {
     "lsbm_edit_encode_emit_dev": (_int, _ENCODE_INPUTS + [_vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp]),
 }
 
+# every symbol include/lsbm_probe.h declares
+_PROBE_INPUTS = [_vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64]
+PROBE_SIGNATURES = {
+    "lsbm_probe_plan_dev": (_int, _PROBE_INPUTS + [_vp, _vp, _vp]),
+    "lsbm_probe_emit_dev": (_int, _PROBE_INPUTS + [_vp, _vp, _u64, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -245,7 +252,7 @@ def lib():
                                   + list(GET_SIGNATURES.items()) + list(ITER_SIGNATURES.items())
                                   + list(WRITE_SIGNATURES.items()) + list(LOG_READ_SIGNATURES.items())
                                   + list(MEMCUT_SIGNATURES.items()) + list(TABLE_WRITE_SIGNATURES.items())
-                                  + list(MANIFEST_SIGNATURES.items())):
+                                  + list(MANIFEST_SIGNATURES.items()) + list(PROBE_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)
