@@ -1,7 +1,7 @@
 """SSTable block reader (Block::Iter of lsbm's table/block.cc) on the GPU.
 
 Thin wrappers over include/lsbm_block.h.  Device tensors in, device tensors
-out; every call enqueues on `stream` (default: torch's current stream).
+out; every call runs on `stream` (default: torch's current stream; the contract is engine.py's).
 
     scan(image, handles)              SeekToFirst / Next until !Valid of every
                                       block: entry count, key bytes, value
@@ -22,7 +22,7 @@ buffer plus int64 offsets (key i = keys[off[i], off[i+1])).
 from collections import namedtuple
 
 from ._lib import check, lib
-from .engine import _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch, on_stream
 from .table import kNoCompression, kSnappyCompression
 
 # comparators (include/lsbm_block.h)
@@ -67,6 +67,7 @@ def _n_handles(handles):
     return handles.numel() // 2
 
 
+@on_stream
 def scan(image, handles, stream=None):
     """(counts int64[n, 3] = {entries, key bytes, value bytes}, status int32[n])."""
     torch = _torch()
@@ -80,6 +81,7 @@ def scan(image, handles, stream=None):
     return counts, status
 
 
+@on_stream
 def decode(image, handles, entry_base=None, key_base=None, keys=None, key_offsets=None,
            values=None, stream=None):
     """Returns (keys, key_offsets, values int64[entries, 2], entry_base, status).
@@ -123,6 +125,7 @@ def decode(image, handles, entry_base=None, key_base=None, keys=None, key_offset
     return keys, key_offsets, values, entry_base, status
 
 
+@on_stream
 def seek(image, handles, keys, key_offsets, cmp=BYTEWISE, value_is_handle=False, found=None,
          found_offsets=None, stream=None):
     """Seek(key q) in block q.  Returns SeekResult(state int32[n], pos, key_len
@@ -155,6 +158,7 @@ def seek(image, handles, keys, key_offsets, cmp=BYTEWISE, value_is_handle=False,
     return SeekResult(state, pos, key_len, value, handle, found, found_offsets)
 
 
+@on_stream
 def table_get(image, index_handle, keys, key_offsets, filter=None, verify=True,  # noqa: A002
               cmp=INTERNAL_KEY, bits_per_key=10, bloom_bits_use=15, stream=None):
     """Table::InternalGet (table/table.cc:309-339) for a batch of keys over a
@@ -175,10 +179,6 @@ def table_get(image, index_handle, keys, key_offsets, filter=None, verify=True, 
     key with its own (SaveValue)."""
     torch = _torch()
     from . import bloom, table
-    if stream is not None:  # (the masking between the steps is torch's: on the same stream)
-        with torch.cuda.stream(stream):
-            return table_get(image, index_handle, keys, key_offsets, filter, verify, cmp,
-                             bits_per_key, bloom_bits_use)
     _require_cuda(image, keys, key_offsets, filter)
     _check(image=image, keys=keys, key_offsets=key_offsets)
     n = key_offsets.numel() - 1

@@ -2,7 +2,7 @@
 flush rule and index block of table/table_builder.cc) on the GPU.
 
 Thin wrappers over include/lsbm_block_build.h.  Device tensors in, device
-tensors out; every call enqueues on `stream` (default: torch's current stream).
+tensors out; every call runs on `stream` (default: torch's current stream; the contract is engine.py's).
 
     plan(keys, key_offsets, values, table_first, ...)
                                       where TableBuilder::Add ends each block
@@ -26,7 +26,7 @@ from collections import namedtuple
 
 from ._lib import check, lib
 from .block import INTERNAL_KEY
-from .engine import _check_tensors, _ptr, _raise_on as _raise_on_status, _require_cuda, _stream_ptr, _torch
+from .engine import _check_tensors, _ptr, _raise_on as _raise_on_status, _require_cuda, _stream_ptr, _torch, on_stream
 from .table import kNoCompression
 
 # per-block / per-table status (include/lsbm_block_build.h)
@@ -58,6 +58,7 @@ def _n_entries(key_offsets, values=None):
     return n
 
 
+@on_stream
 def plan(keys, key_offsets, values, table_first, block_size=4096, restart_interval=16, blocks_cap=None,
          stream=None):
     """PlanResult(block_first int64[blocks_cap + 1], block_bytes int64[blocks_cap],
@@ -87,6 +88,7 @@ def plan(keys, key_offsets, values, table_first, block_size=4096, restart_interv
     return PlanResult(block_first, block_bytes, table_block_first, status)
 
 
+@on_stream
 def build(keys, key_offsets, values, value_image, block_first, out, out_handles, restart_interval=16,
           stream=None):
     """Block b = entries [block_first[b], block_first[b+1]) written at the start
@@ -110,6 +112,7 @@ def build(keys, key_offsets, values, value_image, block_first, out, out_handles,
     return built, status
 
 
+@on_stream
 def index_block(keys, key_offsets, block_first, table_block_first, data_handles, cmp=INTERNAL_KEY,
                 out=None, out_handles=None, stream=None):
     """One index block per table (blocks [table_block_first[t],
@@ -144,6 +147,7 @@ def _raise_on(status, what):
     _raise_on_status(status, what, BUILD_OK, STATUS_MESSAGE)
 
 
+@on_stream
 def table_build(keys, key_offsets, values, value_image, cmp=INTERNAL_KEY, block_size=4096,
                 restart_interval=16, bits_per_key=None, compression=kNoCompression, stream=None):
     """TableBuilder (table/table_builder.cc) Add for every entry, then Finish,

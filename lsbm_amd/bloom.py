@@ -1,7 +1,7 @@
 """SSTable bloom filters (util/bloom.cc, table/filter_block.cc of lsbm) on the GPU.
 
 Thin wrappers over include/lsbm_bloom.h.  Device tensors in, device tensors
-out; every call enqueues on `stream` (default: torch's current stream).
+out; every call runs on `stream` (default: torch's current stream; the contract is engine.py's).
 
     hash(data, seed)                  leveldb::Hash (util/hash.cc:18-49), host
     filter_bytes / k_build / k_probe  BloomFilterPolicy's size and probe rules
@@ -21,7 +21,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import check, lib
-from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _ptr, _require_cuda, _stream_ptr, _torch, on_stream
 
 kFilterBaseLg = 11  # table/filter_block.cc:15
 kFilterBase = 1 << kFilterBaseLg
@@ -45,6 +45,7 @@ def k_probe(bits_per_key, bloom_bits_use=15):
     return int(lib().lsbm_bloom_k_probe(int(bits_per_key), int(bloom_bits_use)))
 
 
+@on_stream
 def build_filters(keys, key_offsets, filter_first, filter_out, out, bits_per_key, strip=0,
                   stream=None):
     """Filter f of keys [filter_first[f], filter_first[f+1]) -> out[filter_out[f], ...)."""
@@ -70,6 +71,7 @@ def _probe_out(n, device, may, n_may):
     return may, n_may
 
 
+@on_stream
 def may_match(filters, handles, keys, key_offsets, bits_per_key, bloom_bits_use=15, strip=0,
               stream=None, may=None, n_may=None):
     """Query q: key q against filters[handles[2q], + handles[2q+1]).
@@ -84,6 +86,7 @@ def may_match(filters, handles, keys, key_offsets, bits_per_key, bloom_bits_use=
     return may, n_may
 
 
+@on_stream
 def filter_block_may_match(blocks, handles, data_offsets, keys, key_offsets, bits_per_key,
                            bloom_bits_use=15, strip=0, stream=None, may=None, n_may=None):
     """Query q: FilterBlockReader(blocks[handles[2q], + handles[2q+1]])
@@ -140,6 +143,7 @@ def layout_filter_block(block_start, block_first, bits_per_key):
     return lay
 
 
+@on_stream
 def build_filter_block(keys, key_offsets, block_start, block_first, bits_per_key, strip=0,
                        stream=None):
     """The bytes FilterBlockBuilder::Finish returns, every filter computed in

@@ -38,7 +38,7 @@ from ._lib import check, lib
 from .block import (INTERNAL_KEY, SEEK_BAD_CONTENTS, SEEK_BAD_ENTRY, SEEK_BAD_HANDLE, SEEK_NOT_VALID, SEEK_VALID)
 from .db import (RUN_LEVEL0, UNDECIDED, DbGetResult, TableFile, Version, _collect, _status_ok, find_file, lookup_keys,
                  memtable_probe, new_verdicts, save_value)
-from .engine import _buf, _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _buf, _ptr, _require_cuda, _stream_ptr, _torch, on_stream
 from .manifest import BYTEWISE
 from .table import kBlockTrailerSize
 
@@ -206,6 +206,7 @@ def _probe_inputs(cand, slot_info, use_length, wb_enabled, cursor_keys, cursor_o
                cursor_keys.numel(), _ptr(cursor_offsets), _ptr(keys), keys.numel(), _ptr(key_offsets), n)
 
 
+@on_stream
 def probe_plan(cand, slot_info, use_length, wb_enabled, cursor_keys, cursor_offsets, keys, key_offsets, count=None,
                stream=None):
     """lsbm_probe_plan_dev: (count int32[n], status int32[1]).  cand uint8[n_slots,
@@ -220,6 +221,7 @@ def probe_plan(cand, slot_info, use_length, wb_enabled, cursor_keys, cursor_offs
     return count, status
 
 
+@on_stream
 def probe_emit(cand, slot_info, use_length, wb_enabled, cursor_keys, cursor_offsets, keys, key_offsets, probe_first,
                probe_slot, probe_cap=None, stream=None):
     """lsbm_probe_emit_dev into probe_slot int32[>= probe_cap] at probe_first
@@ -442,6 +444,7 @@ class BufferedVersion:
         torch.cumsum(count, 0, out=first[1:])
         return count, first, st, (use, wb, ckeys, coff)
 
+    @on_stream
     def get(self, user_keys, key_offsets, snapshot, memtables=(), verify=True, stream=None):
         """Version::Get for a batch of user keys at `snapshot`, after `memtables`:
         db.Version.get's signature and result, DbGetResult(status, values,
@@ -456,9 +459,6 @@ class BufferedVersion:
         read; nothing per slot or per sorted table."""
         torch = _torch()
         from . import block, sstable
-        if stream is not None:
-            with torch.cuda.stream(stream):
-                return self.get(user_keys, key_offsets, snapshot, memtables, verify)
         v, dev = self.version, self.device
         keys, offs, st = lookup_keys(user_keys, key_offsets, snapshot)
         n = offs.numel() - 1

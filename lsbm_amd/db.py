@@ -2,8 +2,8 @@
 GPU: the value of key k at snapshot s over memtables and a set of tables.
 
 Thin wrappers over include/lsbm_get.h and the chain between them.  Device
-tensors in, device tensors out; every call enqueues on `stream` (default:
-torch's current stream).
+tensors in, device tensors out; every call runs on `stream` (default:
+torch's current stream; the contract is engine.py's).
 
     lookup_keys(user_keys, key_offsets, snapshot)   LookupKey: user key ||
                                        fixed64(seq << 8 | kTypeValue)
@@ -39,7 +39,7 @@ from ._lib import check, lib
 from .block import (GET_FILTERED, INTERNAL_KEY, SEEK_BAD_CONTENTS, SEEK_BAD_ENTRY, SEEK_BAD_HANDLE, SEEK_NOT_VALID,
                     SEEK_VALID, STATE_MESSAGE)
 from .block_build import FILTER_KEY, kFooterEncodedLength, kTableMagicNumber
-from .engine import _buf, _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _buf, _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch, on_stream
 from .merge import MERGE_BAD_INPUT, MERGE_OK  # noqa: F401 (the status word of every call here)
 from .sstable import GET_BAD_COMPRESSED
 from .table import kBlockTrailerSize
@@ -93,6 +93,7 @@ def _status_ok(status, what):
 # ---------------------------------------------------------------- the kernels
 
 
+@on_stream
 def lookup_keys(user_keys, key_offsets, snapshot, stream=None):
     """(keys uint8, key_offsets int64[n + 1], status int32[1]): LookupKey of
     every user key at `snapshot` (an int, or an int64 device tensor of one
@@ -123,6 +124,7 @@ def new_verdicts(n, dev):
     return (_buf(n, torch.int32, dev), _buf(2 * n, torch.int64, dev).view(n, 2), _buf(n, torch.int32, dev, -1))
 
 
+@on_stream
 def memtable_probe(mem, keys, key_offsets, source_id, verdict, value, where, stream=None):
     """lsbm_memtable_get_dev: MemTable::Get of every undecided lookup key over
     the sorted memtable `mem`, into verdict / value / where.  Returns status
@@ -144,6 +146,7 @@ def memtable_probe(mem, keys, key_offsets, source_id, verdict, value, where, str
     return status
 
 
+@on_stream
 def find_file(bounds, bound_offsets, run_first, run_flags, visible, keys, key_offsets, stream=None):
     """lsbm_find_file_dev: (file int32[n, n_runs], status int32[1]).  File f's
     smallest and largest internal keys are keys 2f and 2f + 1 of bounds /
@@ -167,6 +170,7 @@ def find_file(bounds, bound_offsets, run_first, run_flags, visible, keys, key_of
     return file, status
 
 
+@on_stream
 def save_value(state, key_len, found, found_offsets, value_in, keys, key_offsets, source_id, verdict, value, where,
                stream=None):
     """lsbm_save_value_dev over one round's table reads, into verdict / value /
@@ -186,6 +190,7 @@ def save_value(state, key_len, found, found_offsets, value_in, keys, key_offsets
     return status
 
 
+@on_stream
 def slices_gather(image, slices, where, where_lo, where_hi, out, out_offsets, stream=None):
     """lsbm_slices_gather_dev: image[slices[q]] -> out[out_offsets[q]:] for the
     queries with where_lo <= where[q] < where_hi.  Returns status int32[1]."""
@@ -223,15 +228,12 @@ def _collect(verdict, value, where, images):
     return DbGetResult(verdict, out, offsets, where)
 
 
+@on_stream
 def memtable_get(mem, user_keys, key_offsets, snapshot, stream=None):
     """MemTable::Get(LookupKey(k, snapshot)) for a batch of user keys over one
     sorted memtable: DbGetResult(status, values, value_offsets, where) with
     status FOUND / DELETED / UNDECIDED (the reference returns false) and where
     0 for the decided queries."""
-    torch = _torch()
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return memtable_get(mem, user_keys, key_offsets, snapshot)
     keys, offs, st = lookup_keys(user_keys, key_offsets, snapshot)
     verdict, value, where = new_verdicts(offs.numel() - 1, offs.device)
     st2 = memtable_probe(mem, keys, offs, 0, verdict, value, where)
@@ -462,6 +464,7 @@ class Version:
     def _visible_in_run_order(self):
         return self.visible[self.run_file].contiguous() if self.run_file.numel() else self.visible[:0]
 
+    @on_stream
     def get(self, user_keys, key_offsets, snapshot, memtables=(), verify=True, stream=None):
         """DB::Get for a batch of user keys at `snapshot` (an int, or an int64
         device tensor, one per query) over `memtables` (MemTable, in the order
@@ -475,9 +478,6 @@ class Version:
         lookup key), besides what sstable.read_blocks and torch.unique read."""
         torch = _torch()
         from . import block, bloom, sstable
-        if stream is not None:  # (the masking between the steps is torch's: on the same stream)
-            with torch.cuda.stream(stream):
-                return self.get(user_keys, key_offsets, snapshot, memtables, verify)
         dev = self.arena.device
         keys, offs, st = lookup_keys(user_keys, key_offsets, snapshot)
         n = offs.numel() - 1
@@ -559,6 +559,7 @@ class Version:
         _status_ok(bad, "Version.get")
         return _collect(verdict, value, where, images)
 
+    @on_stream
     def view(self, snapshot, memtables=(), runs=None, verify=True, stream=None):
         """DBImpl::NewIterator at `snapshot` (lsbm/db_impl.cc:1290-): the
         scan.SnapshotView over `memtables` (MemTable, in the order given: mem,
@@ -584,9 +585,6 @@ class Version:
         AddIterators' children pass scan_runs()."""
         torch = _torch()
         from . import block, merge, scan, sstable
-        if stream is not None:
-            with torch.cuda.stream(stream):
-                return self.view(snapshot, memtables, runs, verify)
         dev = self.arena.device
         chosen = list(range(len(self.runs))) if runs is None else [int(r) for r in runs]
         if any(not 0 <= r < len(self.runs) for r in chosen):

@@ -4,6 +4,16 @@ All tensors are device tensors (torch is only device-memory / stream
 plumbing); every call enqueues on `stream` (default: torch's current stream)
 and returns without synchronising.  Nothing here computes on the CPU.
 
+The stream contract, for every callable of the package that takes `stream`
+(each is wrapped in on_stream below): everything the call does -- allocating
+and zero-filling its outputs and scratch, torch glue between kernels, the
+kernel launches, any host read of a count -- happens on `stream`.  The inputs
+must be ready on `stream` (written there, or ordered before it by the caller
+with an event or a synchronise).  The results belong to `stream`: the caller
+orders any later use on another stream, and keeps them alive (or calls
+Tensor.record_stream) until that use is done.  Host-staged entry points
+(crc32c_batch_host*) take no stream and synchronise themselves.
+
   crc32c_fixed(data, stride, length, n_blocks)   lsbm_crc32c_fixed_dev
   crc32c_batch(data, offsets)                    lsbm_crc32c_batch_dev
   crc32c_extents(data, extents)                  lsbm_crc32c_extents_dev
@@ -15,6 +25,8 @@ Each block's result equals crc32c::Extend(init[i] or 0, block_i, n_i)
 (util/crc32c.cc:286-329), Mask()ed when masked=True (util/crc32c.h:31-34).
 """
 import ctypes
+import functools
+import inspect
 
 import numpy as np
 
@@ -31,6 +43,32 @@ def _stream_ptr(stream):
     if stream is None:
         stream = torch.cuda.current_stream()
     return ctypes.c_void_p(stream.cuda_stream)
+
+
+def on_stream(fn):
+    """Decorator of every callable with a `stream` parameter.  Given a stream
+    that is not torch's current one, the call is made again under
+    torch.cuda.stream(stream) with stream=None, so that allocations, fills,
+    torch glue, launches and host reads all go to that stream (the contract in
+    this module's docstring).  With stream=None, or the current stream itself
+    (as inside a graph capture), the call goes straight through."""
+    at = list(inspect.signature(fn).parameters).index("stream")
+
+    @functools.wraps(fn)
+    def call(*args, **kwargs):
+        stream = args[at] if len(args) > at else kwargs.get("stream")
+        if stream is None:
+            return fn(*args, **kwargs)
+        torch = _torch()
+        if stream.cuda_stream == torch.cuda.current_stream().cuda_stream:
+            return fn(*args, **kwargs)
+        if len(args) > at:
+            args = args[:at] + (None,) + args[at + 1:]
+        else:
+            kwargs["stream"] = None
+        with torch.cuda.stream(stream):
+            return fn(*args, **kwargs)
+    return call
 
 
 def _ptr(t):
@@ -77,6 +115,7 @@ def init(device=0):
     check(lib().lsbm_crc32c_init(int(device)), "lsbm_crc32c_init")
 
 
+@on_stream
 def crc32c_fixed(data, stride, length, n_blocks, init=None, masked=False, out=None,
                  stream=None):
     """Block i = data[i*stride : i*stride+length] (uint8 device tensor)."""
@@ -101,6 +140,7 @@ def _check_offsets(data, offsets):
     return offsets.numel() - 1
 
 
+@on_stream
 def crc32c_batch(data, offsets, init=None, masked=False, out=None, stream=None):
     """Block i = data[offsets[i] : offsets[i+1]] (offsets: int64 device tensor)."""
     torch = _torch()
@@ -115,6 +155,7 @@ def crc32c_batch(data, offsets, init=None, masked=False, out=None, stream=None):
     return out
 
 
+@on_stream
 def crc32c_extents(data, extents, init=None, masked=False, out=None, stream=None):
     """Block i = data[ext[2i] : ext[2i] + ext[2i+1]] (int64 {offset, length} pairs)."""
     torch = _torch()
@@ -131,6 +172,7 @@ def crc32c_extents(data, extents, init=None, masked=False, out=None, stream=None
     return out
 
 
+@on_stream
 def crc32c_verify(data, offsets, expect, init=None, masked=False, stream=None):
     """Returns (ok uint8[n], nbad int32[1]) device tensors."""
     torch = _torch()
@@ -183,6 +225,7 @@ def crc32c_batch_host_multi(data, offsets, devices, init=None, masked=False):
     return out
 
 
+@on_stream
 def fill_splitmix64(buf, seed, stream=None):
     """buf[k] = byte k of the splitmix64 stream `seed` (uint8 device tensor)."""
     _require_cuda(buf)
@@ -192,6 +235,7 @@ def fill_splitmix64(buf, seed, stream=None):
     return buf
 
 
+@on_stream
 def stream_read(buf, sink, stream=None):
     _require_cuda(buf, sink)
     check(lib().lsbm_stream_read_dev(_ptr(buf), buf.numel(), _ptr(sink), _stream_ptr(stream)),

@@ -20,7 +20,7 @@ from collections import namedtuple
 import numpy as np
 
 from ._lib import check, lib
-from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _ptr, _require_cuda, _stream_ptr, _torch, on_stream
 
 kBlockSize = 32768  # common/log_format.h:27
 kHeaderSize = 7     # common/log_format.h:30
@@ -51,6 +51,7 @@ def layout_records(payloads):
     return np.frombuffer(bytes(out), dtype=np.uint8).copy(), np.array(heads, dtype=np.int64)
 
 
+@on_stream
 def seal_records(image, headers, stream=None):
     """lsbm_log_seal_dev: write every header's masked CRC in place.
     Returns (masked uint32-as-int32[n], nbad int32[1]) device tensors."""
@@ -64,6 +65,7 @@ def seal_records(image, headers, stream=None):
     return masked, nbad
 
 
+@on_stream
 def verify_records(image, headers, stream=None):
     """lsbm_log_verify_dev: returns (ok uint8[n], nbad int32[1]) device tensors."""
     torch = _torch()
@@ -101,6 +103,7 @@ def _scratch(nbytes, device):
     return _torch().empty(max((nbytes + 7) // 8, 1), dtype=_torch().int64, device=device)
 
 
+@on_stream
 def walk(image, log_at, log_bytes, initial_offset=0, headers_cap=None, stream=None):
     """lsbm_log_read_walk_dev: WalkResult(block_first int64[n_blocks + 1],
     block_end int64[n_blocks, 2], headers int64[headers_cap] or None, n_headers
@@ -124,6 +127,7 @@ def walk(image, log_at, log_bytes, initial_offset=0, headers_cap=None, stream=No
     return WalkResult(block_first, block_end, None if headers is None else headers[:headers_cap], n_headers, status)
 
 
+@on_stream
 def plan(image, log_at, log_bytes, initial_offset, block_first, block_end, headers, ok, stream=None):
     """lsbm_log_read_plan_dev: PlanResult(totals int64[4] = {records, events,
     side bytes, stop offset}, status int32[1], scratch, n_blocks, n_headers);
@@ -142,6 +146,7 @@ def plan(image, log_at, log_bytes, initial_offset, block_first, block_end, heade
     return PlanResult(totals, status, scratch, nb, nh)
 
 
+@on_stream
 def emit(image, log_at, log_bytes, initial_offset, p, side_at, side_cap, records_cap, events_cap, stream=None):
     """lsbm_log_read_emit_dev: EmitResult(records int64[records_cap, 2],
     last_record_offset int64[records_cap], events int64[events_cap, 4], status
@@ -161,6 +166,7 @@ def emit(image, log_at, log_bytes, initial_offset, p, side_at, side_cap, records
     return EmitResult(records, lro, events, status)
 
 
+@on_stream
 def read_records(image, log_bytes=None, initial_offset=0, stream=None):
     """log::Reader(file, reporter, true, initial_offset) over the log in the
     first log_bytes bytes of a uint8 device tensor, until ReadRecord returns
@@ -175,9 +181,6 @@ def read_records(image, log_bytes=None, initial_offset=0, stream=None):
     plan."""
     torch = _torch()
     _require_cuda(image)
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return read_records(image, log_bytes, initial_offset)
     n = image.numel() if log_bytes is None else int(log_bytes)
     if n > image.numel():
         raise ValueError("log_bytes reaches past the image")

@@ -16,7 +16,7 @@ call, so the work is the encode and the parse of one very long record
 from collections import namedtuple
 
 from ._lib import check, lib
-from .engine import _buf, _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _buf, _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch, on_stream
 
 OK, NO_ROOM, BAD_INPUT = 0, 1, 2  # LSBM_MERGE_OK, _NO_ROOM, _BAD_INPUT
 STATUS_MESSAGE = {NO_ROOM: "an output is too small", BAD_INPUT: "bad input"}
@@ -70,6 +70,7 @@ def _check(**ts):
 
 # ---------------------------------------------------------------- decode
 
+@on_stream
 def decode_plan(image, records, span_cap, longest_cap, stream=None):
     """lsbm_edit_decode_plan_dev: DecodePlan(verdict int32[n], fields int64[n,
     13], new_first int64[n + 1], del_first int64[n + 1], totals int64[3] =
@@ -95,6 +96,7 @@ def decode_plan(image, records, span_cap, longest_cap, stream=None):
     return DecodePlan(verdict, fields, new_first, del_first, totals, status, scratch, span_cap)
 
 
+@on_stream
 def decode_emit(image, records, plan, new_cap, del_cap, keys_cap, stream=None):
     """lsbm_edit_decode_emit_dev: DecodeItems(new_items int64[new_cap, 5],
     key_offsets int64[2 new_cap + 1], keys uint8[keys_cap], del_items
@@ -115,6 +117,7 @@ def decode_emit(image, records, plan, new_cap, del_cap, keys_cap, stream=None):
     return DecodeItems(new_items, key_offsets, keys, del_items, status)
 
 
+@on_stream
 def decode_edits(image, records, stream=None):
     """VersionEdit::DecodeFrom of every record image[records[i, 0], +
     records[i, 1]) -- what log.read_records returns -- at once:
@@ -127,9 +130,6 @@ def decode_edits(image, records, stream=None):
     sizes the items."""
     torch = _torch()
     _require_cuda(image, records)
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return decode_edits(image, records)
     records = records.reshape(-1, 2).contiguous()
     n = records.shape[0]
     span, longest = (torch.stack([records[:, 1].sum(), records[:, 1].max()]).cpu().tolist()) if n else (0, 0)
@@ -159,6 +159,7 @@ def _encode_args(fields, names, del_first, del_items, new_first, new_items, keys
             _ptr(new_items), n_new, _ptr(keys), _ptr(key_offsets), keys.numel()), n, n_del, n_new
 
 
+@on_stream
 def encode_plan(fields, names, del_first, del_items, new_first, new_items, keys, key_offsets, out_at=0, stream=None):
     """lsbm_edit_encode_plan_dev: EncodePlan(records int64[n, 2] = {out_at +
     offset, length}, totals int64[1] = {bytes}, status int32[1], scratch)."""
@@ -174,6 +175,7 @@ def encode_plan(fields, names, del_first, del_items, new_first, new_items, keys,
     return EncodePlan(records, totals, status, scratch)
 
 
+@on_stream
 def encode_emit(fields, names, del_first, del_items, new_first, new_items, keys, key_offsets, plan, out, out_at=0,
                 out_cap=None, stream=None):
     """lsbm_edit_encode_emit_dev into out[out_at, out_at + out_cap): status int32[1]."""
@@ -211,6 +213,7 @@ def sort_deleted(del_items, n):
     return first, d.contiguous()
 
 
+@on_stream
 def encode_edits(fields, names=None, del_items=None, new_first=None, new_items=None, keys=None, key_offsets=None,
                  stream=None):
     """VersionEdit::EncodeTo of n edits at once: Encoded(image uint8, records
@@ -224,9 +227,6 @@ def encode_edits(fields, names=None, del_items=None, new_first=None, new_items=N
     keys as decode_edits gives them."""
     torch = _torch()
     _require_cuda(fields)
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return encode_edits(fields, names, del_items, new_first, new_items, keys, key_offsets)
     dev = fields.device
     fields = fields.reshape(-1, FIELD_WORDS).contiguous()
     n = fields.shape[0]
@@ -267,6 +267,7 @@ def _gather_keys(keys, key_offsets, order):
     return out, offs
 
 
+@on_stream
 def snapshot(files, comparator=BYTEWISE, log_number=0, prev_log_number=0, next_file=0, last_sequence=0, write_cursor=0,
              read_cursors=(0, 0, 0, 0), stream=None):
     """VersionSet::WriteSnapshot's record (lsbm/version_set.cc:2217-2246) from a
@@ -276,10 +277,6 @@ def snapshot(files, comparator=BYTEWISE, log_number=0, prev_log_number=0, next_f
     and the four read cursors.  Encoded(image uint8, records int64[1, 2])."""
     torch = _torch()
     _require_cuda(files.numbers)
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return snapshot(files, comparator, log_number, prev_log_number, next_file, last_sequence, write_cursor,
-                            read_cursors)
     dev = files.numbers.device
     n = files.numbers.numel()
     # EncodeTo writes type by type; WriteSnapshot adds level by level: (type, level), then the table's order
@@ -338,6 +335,7 @@ def _failed(status):
     return Recovered(status, False, 0, 0, 0, 0, 0, 0, (0, 0, 0, 0), {})
 
 
+@on_stream
 def recover(image, comparator=BYTEWISE, log_bytes=None, host_files=True, stream=None):
     """The loop of BasicVersionSet::Recover (lsbm/version_set.cc:1987-2116) over
     a MANIFEST image in device memory: Recovered(status -- Status::ToString()
@@ -352,9 +350,6 @@ def recover(image, comparator=BYTEWISE, log_bytes=None, host_files=True, stream=
     torch = _torch()
     from . import log as _log
     _require_cuda(image)
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return recover(image, comparator, log_bytes, host_files)
     r = _log.read_records(image, log_bytes)
     events = r.events.cpu().tolist()
     n = r.records.shape[0]

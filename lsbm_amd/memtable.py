@@ -3,8 +3,8 @@ order and BuildTable of lsbm: DBImpl::RecoverLogFile / WriteLevel0Table,
 lsbm/db_impl.cc:433-540) on the GPU.
 
 Thin wrappers over include/lsbm_memtable.h and the other modules.  Device
-tensors in, device tensors out; every call enqueues on `stream` (default:
-torch's current stream).
+tensors in, device tensors out; every call runs on `stream` (default:
+torch's current stream; the contract is engine.py's).
 
     scan(image, records)               WriteBatch::Iterate of every record:
                                        entries, user-key bytes, status
@@ -51,7 +51,7 @@ from collections import namedtuple
 import numpy as np
 
 from ._lib import check, lib
-from .engine import _buf, _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _buf, _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch, on_stream
 from .log import kBlockSize, kFirstType, kFullType, kHeaderSize, kLastType, kMiddleType
 from .merge import MERGE_OK, PlanResult
 from .table import kNoCompression
@@ -96,6 +96,7 @@ def _n_records(records):
     return records.numel() // 2
 
 
+@on_stream
 def scan(image, records, stream=None):
     """(counts int64[n, 2] = {entries, user-key bytes}, status int32[n])."""
     torch = _torch()
@@ -122,6 +123,7 @@ def bases(counts):
     return entry_base, key_base
 
 
+@on_stream
 def decode(image, records, entry_base=None, key_base=None, keys=None, key_offsets=None, values=None, stream=None):
     """DecodeResult(keys, key_offsets, values int64[entries, 2], max_sequence
     int64[1] (the 64 bits of the unsigned number), status int32[n]).  Record
@@ -160,6 +162,7 @@ def decode(image, records, entry_base=None, key_base=None, keys=None, key_offset
     return DecodeResult(keys, key_offsets, values, max_sequence, status)
 
 
+@on_stream
 def sort(keys, key_offsets, stream=None):
     """merge.PlanResult(source int64[n], out_key_offsets int64[n + 1], counts
     int64[2] = {n, key bytes}, run_status int32[1]): the memtable's iteration
@@ -184,6 +187,7 @@ def sort(keys, key_offsets, stream=None):
     return PlanResult(source, out_off, counts, status)
 
 
+@on_stream
 def sort_segments(keys, key_offsets, seg_first, stream=None):
     """sort over the memtables of one log (lsbm_memtable_sort_segments_dev):
     segment s = entries [seg_first[s], seg_first[s + 1]) (an int64 device
@@ -216,6 +220,7 @@ def max_sequence_of(t):
     return int(t.cpu()[0]) & ((1 << 64) - 1)
 
 
+@on_stream
 def entries(image, records, paranoid=False, stream=None):
     """What the reference's memtable holds after InsertInto of every record, in
     NewIterator()'s order: EntriesResult(keys, key_offsets, values int64[n, 2],
@@ -227,9 +232,6 @@ def entries(image, records, paranoid=False, stream=None):
     reference's message."""
     torch = _torch()
     from . import merge
-    if stream is not None:  # (the sums between the steps are torch's: on the same stream)
-        with torch.cuda.stream(stream):
-            return entries(image, records, paranoid)
     counts, _ = scan(image, records)
     entry_base, key_base = bases(counts)
     d = decode(image, records, entry_base, key_base)
@@ -249,6 +251,7 @@ def entries(image, records, paranoid=False, stream=None):
     return EntriesResult(g.keys, g.key_offsets, g.values, d.status, max_sequence_of(d.max_sequence))
 
 
+@on_stream
 def flush(image, records, compression=kNoCompression, block_size=4096, restart_interval=16, bits_per_key=None,
           paranoid=False, stream=None):
     """BuildTable (lsbm/builder.cc:36-48) over the memtable of `records`:
@@ -259,12 +262,8 @@ def flush(image, records, compression=kNoCompression, block_size=4096, restart_i
     internal key as bytes (FileMetaData), as the table writer's TablesResult
     has them.  Without an entry no table is written: image, data_handles,
     index_handle, smallest and largest are None."""
-    torch = _torch()
     from . import sstable
     from .block import INTERNAL_KEY
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return flush(image, records, compression, block_size, restart_interval, bits_per_key, paranoid)
     e = entries(image, records, paranoid)
     n = e.key_offsets.numel() - 1
     if n == 0:
@@ -302,6 +301,7 @@ def _max_sequences(image, records, mem_of, n_mems):
     return best ^ flip
 
 
+@on_stream
 def flush_many(image, records, mem_first, compression=kNoCompression, block_size=4096, restart_interval=16,
                bits_per_key=None, paranoid=False, stream=None):
     """flush for the memtables of one cut list in one chain: memtable m is
@@ -315,10 +315,6 @@ def flush_many(image, records, mem_first, compression=kNoCompression, block_size
     torch = _torch()
     from . import merge, sstable
     from .block import INTERNAL_KEY
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return flush_many(image, records, mem_first, compression, block_size, restart_interval, bits_per_key,
-                              paranoid)
     mem_first = [int(x) for x in mem_first]
     n, n_mems = _n_records(records), len(mem_first) - 1
     if n_mems < 0 or mem_first[0] != 0 or mem_first[-1] != n or any(a > b for a, b in zip(mem_first, mem_first[1:])):
@@ -386,6 +382,7 @@ def _framing(buf):
     return out
 
 
+@on_stream
 def log_records(image_host, device="cuda", stream=None):
     """(image, records): the logical records of a log file (bytes or a uint8
     numpy array) as log::Reader::ReadRecord returns them, for scan / entries /
@@ -396,9 +393,6 @@ def log_records(image_host, device="cuda", stream=None):
     A framing or CRC fault raises ValueError."""
     torch = _torch()
     from . import log
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return log_records(image_host, device)
     buf = np.frombuffer(bytes(image_host), dtype=np.uint8) if isinstance(image_host, (bytes, bytearray)) \
         else np.ascontiguousarray(image_host, dtype=np.uint8)
     physical = _framing(buf)
@@ -443,6 +437,7 @@ def log_records(image_host, device="cuda", stream=None):
     return image, rec
 
 
+@on_stream
 def recover_log(image_host, compression=kNoCompression, block_size=4096, restart_interval=16, bits_per_key=None,
                 paranoid=False, device="cuda", stream=None):
     """RecoverLogFile for a log that fits one memtable: log_records, then flush."""
@@ -450,6 +445,7 @@ def recover_log(image_host, compression=kNoCompression, block_size=4096, restart
     return flush(image, records, compression, block_size, restart_interval, bits_per_key, paranoid, stream)
 
 
+@on_stream
 def recover(image, paranoid=False, compression=kNoCompression, block_size=4096, restart_interval=16,
             bits_per_key=None, stream=None, log_bytes=None):
     """DBImpl::RecoverLogFile (lsbm/db_impl.cc:398-470) for a log that lies in
@@ -466,11 +462,7 @@ def recover(image, paranoid=False, compression=kNoCompression, block_size=4096, 
     returned before the reporting call are inserted, the one that call returned
     is not; a record that WriteBatch::Iterate rejects raises ValueError with the
     reference's message, as flush(paranoid=True) does."""
-    torch = _torch()
     from . import log
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return recover(image, paranoid, compression, block_size, restart_interval, bits_per_key, None, log_bytes)
     r = log.read_records(image, log_bytes)
     records, status = r.records, None
     if paranoid and r.events.shape[0]:
@@ -482,6 +474,7 @@ def recover(image, paranoid=False, compression=kNoCompression, block_size=4096, 
     return RecoverResult(f, r.events, status)
 
 
+@on_stream
 def heights(n, rnd=SKIPLIST_SEED, stream=None, device="cuda"):
     """(heights uint8[n], rnd_out int64[1]): SkipList::RandomHeight of n
     consecutive inserts from generator state rnd (a new memtable's by default),
@@ -501,6 +494,7 @@ def clip_write_buffer(write_buffer_size):
     return min(max(int(write_buffer_size), kMinWriteBuffer), kMaxWriteBuffer)
 
 
+@on_stream
 def cut(key_offsets, values, entry_base, mode, write_buffer_size, key_extra=0, types=None, rec_status=None,
         state=None, mem_cap=None, usage=None, mem_first=None, mem_usage=None, counts=None, state_out=None,
         status=None, stream=None):
@@ -551,6 +545,7 @@ def cut(key_offsets, values, entry_base, mode, write_buffer_size, key_extra=0, t
     return CutResult(usage, mem_first, mem_usage, counts, state_out, status)
 
 
+@on_stream
 def recover_all(image, write_buffer_size=4 << 20, paranoid=False, compression=kNoCompression, block_size=4096,
                 restart_interval=16, bits_per_key=None, stream=None, log_bytes=None):
     """DBImpl::RecoverLogFile (lsbm/db_impl.cc:398-479) for a log of any size in
@@ -569,10 +564,6 @@ def recover_all(image, write_buffer_size=4 << 20, paranoid=False, compression=kN
     progress is not (RecoverLogFile returns before its WriteLevel0Table)."""
     torch = _torch()
     from . import log
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return recover_all(image, write_buffer_size, paranoid, compression, block_size, restart_interval,
-                               bits_per_key, None, log_bytes)
     r = log.read_records(image, log_bytes)
     records, status = r.records, None
     if paranoid and r.events.shape[0]:

@@ -2,7 +2,7 @@
 and the output-file cut of DoCompactionWork, lsbm/db_impl.cc) on the GPU.
 
 Thin wrappers over include/lsbm_merge.h.  Device tensors in, device tensors
-out; every call enqueues on `stream` (default: torch's current stream).
+out; every call runs on `stream` (default: torch's current stream; the contract is engine.py's).
 
     plan(keys, key_offsets, run_first, ...)
                                       which input entry becomes which output
@@ -30,7 +30,7 @@ from collections import namedtuple
 
 from ._lib import check, lib
 from .block import BYTEWISE, INTERNAL_KEY
-from .engine import _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch, on_stream
 from .table import kNoCompression
 
 # per-run status (include/lsbm_merge.h)
@@ -70,6 +70,7 @@ def _flags(cmp, drop, smallest_snapshot, bottom_level):
     return MERGE_DROP | (MERGE_BOTTOM_LEVEL if bottom_level else 0), int(smallest_snapshot)
 
 
+@on_stream
 def plan(keys, key_offsets, run_first, cmp=INTERNAL_KEY, drop=False, smallest_snapshot=None, bottom_level=False,
          stream=None):
     """PlanResult(source int64[n], out_key_offsets int64[n + 1], counts int64[2]
@@ -97,6 +98,7 @@ def plan(keys, key_offsets, run_first, cmp=INTERNAL_KEY, drop=False, smallest_sn
     return PlanResult(source, out_off, counts, run_status)
 
 
+@on_stream
 def gather(keys, key_offsets, values, plan_result, out_keys=None, out_key_offsets=None, out_values=None,
            stream=None):
     """GatherResult(keys, key_offsets, values int64[cap, 2], status int32[1]).
@@ -128,6 +130,7 @@ def gather(keys, key_offsets, values, plan_result, out_keys=None, out_key_offset
     return GatherResult(out_keys, out_key_offsets, out_values, status)
 
 
+@on_stream
 def merge(keys, key_offsets, values, run_first, cmp=INTERNAL_KEY, drop=False, smallest_snapshot=None,
           bottom_level=False, stream=None):
     """MergeResult(keys, key_offsets int64[n_out + 1], values int64[n_out, 2],
@@ -135,10 +138,6 @@ def merge(keys, key_offsets, values, run_first, cmp=INTERNAL_KEY, drop=False, sm
     to back; the one device -> host read (n_out and the key bytes, to trim the
     tensors) comes after both.  With a run in error the output is empty and
     run_status says why."""
-    torch = _torch()
-    if stream is not None:  # (the trimming is torch's: on the same stream)
-        with torch.cuda.stream(stream):
-            return merge(keys, key_offsets, values, run_first, cmp, drop, smallest_snapshot, bottom_level)
     _require_cuda(values)
     values = values.reshape(-1)
     p = plan(keys, key_offsets, run_first, cmp, drop, smallest_snapshot, bottom_level)
@@ -181,6 +180,7 @@ def index_data_handles(image, index_handle):
     return sstable._index_data_handles(image, index_handle, None, sstable._in_place)
 
 
+@on_stream
 def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None, cmp=INTERNAL_KEY, drop=False,
             smallest_snapshot=None, bottom_level=False, block_size=4096, restart_interval=16, bits_per_key=None,
             stream=None):
@@ -202,12 +202,7 @@ def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None
     touches the host; the host reads counts and block sizes.  Returns
     [OutputTable(image, data_handles, index_handle)]; the images are views of
     one arena, so holding one keeps the whole arena alive."""
-    torch = _torch()
     from . import sstable
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return compact(images, data_handles, max_file_size, index_handles, cmp, drop, smallest_snapshot,
-                           bottom_level, block_size, restart_interval, bits_per_key)
     return sstable._compact(sstable._in_place, images, data_handles, max_file_size, index_handles, cmp, drop,
                             smallest_snapshot, bottom_level, block_size, restart_interval, bits_per_key,
                             kNoCompression, None)

@@ -2,8 +2,8 @@
 SeekToFirst / SeekToLast / Next / Prev / status) on the GPU.
 
 Thin wrappers over include/lsbm_iter.h and the chain between them.  Device
-tensors in, device tensors out; every call enqueues on `stream` (default:
-torch's current stream).
+tensors in, device tensors out; every call runs on `stream` (default:
+torch's current stream; the contract is engine.py's).
 
     plan(keys, key_offsets, snapshot)   the snapshot view of sorted entries:
                                        which merged positions a DBIter at
@@ -37,7 +37,8 @@ Prev() while key() >= lo; both stop after `limit` entries.
 from collections import namedtuple
 
 from ._lib import check, lib
-from .engine import _buf, _check_tensors, _ptr, _raise_on as _raise_on_status, _require_cuda, _stream_ptr, _torch
+from .engine import (_buf, _check_tensors, _ptr, _raise_on as _raise_on_status, _require_cuda, _stream_ptr, _torch,
+                     on_stream)
 from .merge import MERGE_BAD_INPUT, MERGE_NO_ROOM, MERGE_OK, MERGE_UNSORTED, PlanResult, kMaxSequenceNumber
 from . import merge as _merge
 
@@ -81,6 +82,7 @@ def _snapshot(snapshot):
     return snapshot
 
 
+@on_stream
 def plan(keys, key_offsets, snapshot, stream=None):
     """ViewPlan(source int64[n] = live, out_key_offsets int64[n + 1], counts
     int64[3] = {n_yield, live key bytes, corrupt entries}, yield_rank int64[n +
@@ -112,6 +114,7 @@ def plan(keys, key_offsets, snapshot, stream=None):
     return ViewPlan(source, out_off, counts, yield_rank, corrupt_rank, first, back, status)
 
 
+@on_stream
 def view(keys, key_offsets, values, value_image, snapshot, stream=None):
     """The SnapshotView of sorted entries at `snapshot`: plan, merge.gather of
     the live entries (plan's source / out_key_offsets / counts are a merge
@@ -119,9 +122,6 @@ def view(keys, key_offsets, values, value_image, snapshot, stream=None):
     (the status words and n_yield) follows the three.  Raises ValueError for
     entries that are not sorted or not well formed."""
     torch = _torch()
-    if stream is not None:  # (the cumsum and the trimming are torch's: on the same stream)
-        with torch.cuda.stream(stream):
-            return view(keys, key_offsets, values, value_image, snapshot)
     _require_cuda(keys, key_offsets, values, value_image)
     values = values.reshape(-1)
     _check(keys=keys, key_offsets=key_offsets, values=values, value_image=value_image)
@@ -181,6 +181,7 @@ class SnapshotView:
             raise ValueError("hi_present without hi")
         return q, lo, lo_offsets, hi, hi_offsets, lo_present, hi_present
 
+    @on_stream
     def range(self, lo=None, lo_offsets=None, hi=None, hi_offsets=None, limit=None, reverse=False, lo_present=None,
               hi_present=None, stream=None):
         """RangeResult(j_begin int64[q], count int64[q], status int32[q],
@@ -216,6 +217,7 @@ class SnapshotView:
             _ptr(value_bytes), _ptr(call_status), _stream_ptr(stream)), "lsbm_dbiter_range_dev")
         return RangeResult(j_begin, count, status, key_bytes, value_bytes, call_status)
 
+    @on_stream
     def emit(self, j_begin, entry_first, key_first, value_first, reverse=False, out_keys=None, out_key_offsets=None,
              out_values=None, out_value_offsets=None, totals=None, stream=None):
         """lsbm_dbiter_emit_dev: (keys, key_offsets, values, value_offsets,
@@ -248,6 +250,7 @@ class SnapshotView:
             cap, _ptr(status), _stream_ptr(stream)), "lsbm_dbiter_emit_dev")
         return out_keys, out_key_offsets, out_values, out_value_offsets, status
 
+    @on_stream
     def scan(self, lo=None, lo_offsets=None, hi=None, hi_offsets=None, limit=None, reverse=False, lo_present=None,
              hi_present=None, stream=None):
         """ScanResult(status int32[q], entry_first int64[q + 1], keys uint8,
@@ -258,9 +261,6 @@ class SnapshotView:
         range, three cumsums over the queries, one host read of the three
         totals (and the call's status word) to size the outputs, then emit."""
         torch = _torch()
-        if stream is not None:  # (the cumsums are torch's: on the same stream)
-            with torch.cuda.stream(stream):
-                return self.scan(lo, lo_offsets, hi, hi_offsets, limit, reverse, lo_present, hi_present)
         r = self.range(lo, lo_offsets, hi, hi_offsets, limit, reverse, lo_present, hi_present)
         q = r.count.numel()
         dev = r.count.device
@@ -277,13 +277,16 @@ class SnapshotView:
         _raise_on(st, "emit")
         return ScanResult(r.status, sums[0], keys, key_offsets, values, value_offsets)
 
+    @on_stream
     def seek(self, keys, offsets, stream=None):
         """DBIter::Seek(k) for a batch of user keys: the first yielded entry at or after each, if any."""
         return self.scan(keys, offsets, limit=1, stream=stream)
 
+    @on_stream
     def seek_to_first(self, stream=None):
         return self._end(False, stream)
 
+    @on_stream
     def seek_to_last(self, stream=None):
         return self._end(True, stream)
 

@@ -2,7 +2,7 @@
 format) on the GPU.
 
 Thin wrappers over include/lsbm_snappy.h.  Device tensors in, device tensors
-out; every call enqueues on `stream` (default: torch's current stream).
+out; every call runs on `stream` (default: torch's current stream; the contract is engine.py's).
 
     max_compressed_length(n)           snappy::MaxCompressedLength
     compress(data, offsets)            RawCompress of every block, one launch
@@ -18,7 +18,7 @@ out; every call enqueues on `stream` (default: torch's current stream).
 Blocks are a uint8 buffer plus int64 offsets (block i = data[off[i], off[i+1])).
 """
 from ._lib import check, lib
-from .engine import _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch, on_stream
 
 # The most a snappy stream of c bytes can expand to: a 3-byte copy tag emits
 # at most 64 bytes (21.3x).  A preamble claiming more cannot be met, so
@@ -36,6 +36,7 @@ def max_compressed_length(n):
     return int(lib().lsbm_snappy_max_compressed_length(int(n)))
 
 
+@on_stream
 def compress(data, offsets, out=None, out_offsets=None, out_len=None, stream=None):
     """Compress every block.  Returns (out, out_offsets, out_len): block i's
     compressed bytes are out[out_offsets[i], out_offsets[i] + out_len[i]).
@@ -64,6 +65,7 @@ def compress(data, offsets, out=None, out_offsets=None, out_len=None, stream=Non
     return out, out_offsets, out_len[:n]
 
 
+@on_stream
 def uncompressed_length(data, offsets, stream=None):
     """(ulen, ok) per block: GetUncompressedLength."""
     torch = _torch()
@@ -78,6 +80,7 @@ def uncompressed_length(data, offsets, stream=None):
     return ulen[:n], ok[:n]
 
 
+@on_stream
 def uncompress(data, offsets, out=None, out_offsets=None, ok=None, n_bad=None, stream=None):
     """RawUncompress every block.  Returns (out, out_offsets, ok, n_bad):
     block i's output is out[out_offsets[i], out_offsets[i+1]), ok[i] = 1 on

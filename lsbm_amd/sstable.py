@@ -3,8 +3,8 @@ GPU: TableBuilder::WriteBlock's keep rule and ReadBlock's type switch of lsbm's
 table/ layer, and the table writer, Get and compaction built on them.
 
 Thin wrappers over include/lsbm_table_pack.h and the other modules.  Device
-tensors in, device tensors out; every call enqueues on `stream` (default:
-torch's current stream).
+tensors in, device tensors out; every call runs on `stream` (default:
+torch's current stream; the contract is engine.py's).
 
     pack_plan(raw_len, comp_len, ...)  the keep rule (table/table_builder.cc:187)
                                        and the offsets that follow from it
@@ -45,7 +45,7 @@ import numpy as np
 from ._lib import check, lib
 from .block import (BYTEWISE, GET_BAD_CHECKSUM, GET_BAD_TYPE, GET_FILTERED, INTERNAL_KEY, SEEK_BAD_HANDLE,
                     SEEK_VALID)
-from .engine import _buf, _check_tensors, _ptr, _raise_on, _require_cuda, _stream_ptr, _torch
+from .engine import _buf, _check_tensors, _ptr, _raise_on, _require_cuda, _stream_ptr, _torch, on_stream
 from .merge import OutputTable
 from .table import kBlockTrailerSize, kNoCompression, kSnappyCompression, seal_blocks
 
@@ -94,6 +94,7 @@ def keep_compressed(raw_len, comp_len):
     return comp_len != mask and comp_len < ((raw_len - raw_len // 8) & mask)
 
 
+@on_stream
 def pack_plan(raw_len, comp_len=None, first_offset=0, gap=kBlockTrailerSize, stream=None):
     """(types uint8[n], handles int64[2n], end int64[1]): type[i] = 1 where the
     compressed form is kept (comp_len[i] < raw_len[i] - raw_len[i] / 8; comp_len
@@ -116,6 +117,7 @@ def pack_plan(raw_len, comp_len=None, first_offset=0, gap=kBlockTrailerSize, str
     return types, handles, end
 
 
+@on_stream
 def pack(raw, raw_handles, comp, comp_offsets, types, handles, out, gap=kBlockTrailerSize, stream=None):
     """Block i: handles[2i+1] bytes to out[handles[2i]:], from raw[raw_handles[2i]:]
     where types[i] == 0 and from comp[comp_offsets[i]:] where it is 1 (comp /
@@ -159,6 +161,7 @@ def _preamble(image, off, size):
     return torch.where(ok, ulen, torch.zeros_like(ulen)), ok
 
 
+@on_stream
 def read_blocks(image, handles, verify=True, max_bytes=1 << 30, stream=None):
     """Batched ReadBlock (table/format.cc:66-148) of the blocks `handles` names
     in the file image, in the reference's order of checks: the handle plus its
@@ -180,9 +183,6 @@ def read_blocks(image, handles, verify=True, max_bytes=1 << 30, stream=None):
     the compressed bytes."""
     torch = _torch()
     from . import snappy, table
-    if stream is not None:  # (the masking between the steps is torch's: on the same stream)
-        with torch.cuda.stream(stream):
-            return read_blocks(image, handles, verify, max_bytes)
     _require_cuda(image, handles)
     _check(image=image, handles=handles)
     if handles.numel() % 2:
@@ -300,6 +300,7 @@ def _n_tables(table_block_first):
     return table_block_first.numel() - 1
 
 
+@on_stream
 def pack_plan_tables(raw_len, comp_len, table_block_first, first_offset=None, gap=kBlockTrailerSize, types=None,
                      handles=None, end=None, status=None, stream=None):
     """pack_plan with the running offset restarting at every table
@@ -326,6 +327,7 @@ def pack_plan_tables(raw_len, comp_len, table_block_first, first_offset=None, ga
     return types, handles, end, status
 
 
+@on_stream
 def filter_layout(block_first, table_block_first, data_handles, data_end, bits_per_key, out=None, out_handles=None,
                   filters_cap=0, stream=None):
     """FilterBlockBuilder's layout for every table (lsbm_filter_layout_dev):
@@ -358,6 +360,7 @@ def filter_layout(block_first, table_block_first, data_handles, data_end, bits_p
     return FilterLayout(size, count, first, out_f, status)
 
 
+@on_stream
 def metaindex_blocks(data_end, filter_size=None, out=None, out_handles=None, stream=None):
     """One metaindex block per table (lsbm_metaindex_build_dev): (sizes
     int64[T], status int32[T]); with out / out_handles the bytes too."""
@@ -375,6 +378,7 @@ def metaindex_blocks(data_end, filter_size=None, out=None, out_handles=None, str
     return sizes, status
 
 
+@on_stream
 def place_tables(data_handles, table_block_first, tail_handles, tail_per_table, tail_end, table_base, arena,
                  stream=None):
     """Footers and placement (lsbm_table_place_dev): PlacedTables(table_size
@@ -405,6 +409,7 @@ def _worst(*statuses):
     return torch.cat(live).max().reshape(1) if live else None
 
 
+@on_stream
 def finish_tables(keys, key_offsets, block_first, table_block_first, blocks, cmp=INTERNAL_KEY, restart_interval=16,
                   bits_per_key=None, compression=kSnappyCompression, stream=None):
     """TableBuilder from the first WriteBlock to the footer for every table of
@@ -420,10 +425,6 @@ def finish_tables(keys, key_offsets, block_first, table_block_first, blocks, cmp
     blocks: the staging sizes, the arena's size, and the results."""
     torch = _torch()
     from . import block_build, bloom, snappy
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return finish_tables(keys, key_offsets, block_first, table_block_first, blocks, cmp, restart_interval,
-                                 bits_per_key, compression)
     if compression not in (kNoCompression, kSnappyCompression):
         raise ValueError("unknown compression type")
     if cmp not in (BYTEWISE, INTERNAL_KEY):
@@ -580,6 +581,7 @@ def _build_blocks(keys, key_offsets, values, value_image, p, restart_interval, c
     return block_first, blocks
 
 
+@on_stream
 def write_tables(keys, key_offsets, values, value_image, table_first, cmp=INTERNAL_KEY, block_size=4096,
                  restart_interval=16, bits_per_key=None, compression=kSnappyCompression, stream=None):
     """TableBuilder (table/table_builder.cc) Add for every entry, then Finish,
@@ -599,10 +601,6 @@ def write_tables(keys, key_offsets, values, value_image, table_first, cmp=INTERN
         raise ValueError("unknown compression type")
     if cmp not in (BYTEWISE, INTERNAL_KEY):
         raise ValueError("unknown comparator")
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return write_tables(keys, key_offsets, values, value_image, table_first, cmp, block_size,
-                                restart_interval, bits_per_key, compression)
     _require_cuda(keys, key_offsets, values, value_image)
     dev = keys.device
     n = key_offsets.numel() - 1
@@ -619,6 +617,7 @@ def write_tables(keys, key_offsets, values, value_image, table_first, cmp=INTERN
                          bits_per_key, compression)
 
 
+@on_stream
 def write_table(keys, key_offsets, values, value_image, cmp=INTERNAL_KEY, block_size=4096, restart_interval=16,
                 bits_per_key=None, compression=kSnappyCompression, stream=None):
     """write_tables of one table: (file_image uint8 device tensor, data_handles
@@ -646,6 +645,7 @@ def _get_state_of(read_status):
     return out
 
 
+@on_stream
 def table_get(image, index_handle, keys, key_offsets, filter=None, verify=True,  # noqa: A002
               cmp=INTERNAL_KEY, bits_per_key=10, bloom_bits_use=15, max_bytes=1 << 30, stream=None):
     """Table::InternalGet (table/table.cc:309-339) for a batch of keys over a
@@ -663,10 +663,6 @@ def table_get(image, index_handle, keys, key_offsets, filter=None, verify=True, 
     state."""
     torch = _torch()
     from . import block, bloom
-    if stream is not None:  # (the masking between the steps is torch's: on the same stream)
-        with torch.cuda.stream(stream):
-            return table_get(image, index_handle, keys, key_offsets, filter, verify, cmp, bits_per_key,
-                             bloom_bits_use, max_bytes)
     _require_cuda(image, keys, key_offsets, filter)
     _check(image=image, keys=keys, key_offsets=key_offsets, filter=filter)
     n = key_offsets.numel() - 1
@@ -832,6 +828,7 @@ def _compact(read, images, data_handles, max_file_size, index_handles, cmp, drop
             for t in range(len(table_first) - 1)]
 
 
+@on_stream
 def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None, cmp=INTERNAL_KEY, drop=False,
             smallest_snapshot=None, bottom_level=False, block_size=4096, restart_interval=16, bits_per_key=None,
             compression=kNoCompression, verify=True, stream=None):
@@ -844,10 +841,5 @@ def compact(images, data_handles=None, max_file_size=2 << 20, index_handles=None
     finish_tables finishes every output table from its slice of those blocks in
     one chain.  Returns [OutputTable(image, data_handles, index_handle)]; the
     images are views of one arena, so holding one keeps the whole arena alive."""
-    torch = _torch()
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return compact(images, data_handles, max_file_size, index_handles, cmp, drop, smallest_snapshot,
-                           bottom_level, block_size, restart_interval, bits_per_key, compression, verify)
     return _compact(read_blocks, images, data_handles, max_file_size, index_handles, cmp, drop, smallest_snapshot,
                     bottom_level, block_size, restart_interval, bits_per_key, compression, verify)

@@ -19,7 +19,7 @@ import ctypes
 import numpy as np
 
 from ._lib import LSBM_BLOCK_TRAILER_SIZE, check, lib
-from .engine import _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _ptr, _require_cuda, _stream_ptr, _torch, on_stream
 
 kBlockTrailerSize = LSBM_BLOCK_TRAILER_SIZE  # table/format.h:84
 kNoCompression = 0x0  # include/leveldb/options.h:27
@@ -77,6 +77,7 @@ def _check_image(file_image, handles, types=None):
     return n
 
 
+@on_stream
 def seal_blocks(file_image, handles, types, stream=None, nbad=None):
     """Batched WriteRawBlock trailers: writes file_image[off+size : off+size+5].
     Handles whose size + 5 bytes fall outside the image are left alone and
@@ -91,6 +92,7 @@ def seal_blocks(file_image, handles, types, stream=None, nbad=None):
     return nbad
 
 
+@on_stream
 def trailer_crcs(file_image, handles, types, stream=None, out=None, nbad=None):
     """Batched WriteRawBlock CRCs without touching the image: returns (masked
     int32[n], nbad int32[1]); masked[i] is the trailer's crc field
@@ -107,6 +109,7 @@ def trailer_crcs(file_image, handles, types, stream=None, out=None, nbad=None):
     return out, nbad
 
 
+@on_stream
 def verify_blocks(file_image, handles, stream=None):
     """Batched ReadBlock verify: returns (ok uint8[n], nbad int32[1]).  A
     handle past the image (truncated block read) is not ok."""
@@ -125,6 +128,7 @@ def read_block_status(ok_flag):
     return Status.OK() if ok_flag else Status.Corruption("block checksum mismatch")
 
 
+@on_stream
 def verify_status(file_image, handles, stream=None):
     """First failing block's Status, like a sequence of ReadBlock calls."""
     ok, nbad = verify_blocks(file_image, handles, stream)

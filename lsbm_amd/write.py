@@ -3,7 +3,7 @@ WriteBatchInternal::Append / SetSequence, log::Writer::AddRecord of lsbm:
 lsbm/db_impl.cc:1321-1441, common/write_batch.cc, common/log_writer.cc) on the GPU.
 
 Thin wrappers over include/lsbm_write.h.  Device tensors in, device tensors
-out; every call enqueues on `stream` (default: torch's current stream).
+out; every call runs on `stream` (default: torch's current stream; the contract is engine.py's).
 
     sizes(types, key_offsets, ...)   every op's encoded size as running sums,
                                      and the running sums of the batches' ByteSize
@@ -36,7 +36,7 @@ logfile_->Sync() itself (group_sync says where it falls).
 from collections import namedtuple
 
 from ._lib import check, lib
-from .engine import _buf, _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch
+from .engine import _buf, _check_tensors, _ptr, _require_cuda, _stream_ptr, _torch, on_stream
 from .log import kBlockSize, kHeaderSize
 
 OK, NO_ROOM, BAD_INPUT = 0, 1, 2  # LSBM_MERGE_OK, _NO_ROOM, _BAD_INPUT
@@ -77,6 +77,7 @@ def _raise(code, what):
         raise ValueError(f"{what}: {STATUS_MESSAGE.get(code, code)}")
 
 
+@on_stream
 def sizes(types, key_offsets, keys_size, values, value_image_size, batch_first, op_sum=None, batch_sum=None,
           stream=None):
     """SizesResult(op_sum int64[n_ops + 1], batch_sum int64[n_writers + 1],
@@ -102,6 +103,7 @@ def sizes(types, key_offsets, keys_size, values, value_image_size, batch_first, 
     return SizesResult(op_sum, batch_sum, status)
 
 
+@on_stream
 def group(batch_bytes=None, sync=None, batch_sum=None, group_first=None, group_sync=None, stream=None):
     """GroupResult(group_first int64[cap + 1], group_sync uint8[cap], n_groups
     int64[1], status): group g is writers [group_first[g], group_first[g + 1]).
@@ -134,6 +136,7 @@ def group(batch_bytes=None, sync=None, batch_sum=None, group_first=None, group_s
     return GroupResult(group_first, group_sync, n_groups, status)
 
 
+@on_stream
 def build(types, keys, key_offsets, value_image, values, batch_first, op_sum, group_first, n_groups, last_sequence=0,
           reps=None, records=None, seq_counts=None, stream=None):
     """BuildResult(reps uint8, records int64[2 n_groups], seq_counts
@@ -169,6 +172,7 @@ def build(types, keys, key_offsets, value_image, values, batch_first, op_sum, gr
     return BuildResult(reps, records, seq_counts, new_last, status)
 
 
+@on_stream
 def frame_plan(records, image_size, log_offset=0, frag_first=None, rec_start=None, stream=None):
     """FramePlan(frag_first int64[n + 1], rec_start int64[n + 1], status):
     record i is physical records [frag_first[i], frag_first[i + 1]) and its
@@ -192,6 +196,7 @@ def frame_plan(records, image_size, log_offset=0, frag_first=None, rec_start=Non
     return FramePlan(frag_first, rec_start, status)
 
 
+@on_stream
 def frame(image, records, log_offset, frag_first, rec_start, out=None, headers=None, stream=None):
     """FrameResult(out uint8, headers int64, status): the bytes appended at file
     offset log_offset (out[0] is that offset) with zero CRC fields, and every
@@ -216,6 +221,7 @@ def frame(image, records, log_offset, frag_first, rec_start, out=None, headers=N
     return FrameResult(out, headers, status)
 
 
+@on_stream
 def frame_records(image, records, log_offset=0, seal=True, stream=None):
     """log::Writer::AddRecord of every record image[records[2i], + records[2i+1])
     onto a log of log_offset bytes: FramedRecords(log uint8, headers int64,
@@ -225,9 +231,6 @@ def frame_records(image, records, log_offset=0, seal=True, stream=None):
     status), one after."""
     torch = _torch()
     from . import log as _log
-    if stream is not None:  # (the reads between the steps are torch's: on the same stream)
-        with torch.cuda.stream(stream):
-            return frame_records(image, records, log_offset, seal)
     p = frame_plan(records, image.numel(), log_offset)
     n_frag, end, st = torch.stack([p.frag_first[-1], p.rec_start[-1], p.status[0].to(torch.int64)]).cpu().tolist()
     _raise(st, "frame_plan")
@@ -240,6 +243,7 @@ def frame_records(image, records, log_offset=0, seal=True, stream=None):
     return FramedRecords(out, headers, end)
 
 
+@on_stream
 def write_batches(types, keys, key_offsets, value_image, values, batch_first, sync=None, last_sequence=0,
                   log_offset=0, stream=None):
     """DBImpl::Write of every queued writer until the queue has drained:
@@ -255,10 +259,6 @@ def write_batches(types, keys, key_offsets, value_image, values, batch_first, sy
     physical record count and the end offset after `frame_plan`."""
     torch = _torch()
     from . import log as _log
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return write_batches(types, keys, key_offsets, value_image, values, batch_first, sync, last_sequence,
-                                 log_offset)
     dev = key_offsets.device
     s = sizes(types, key_offsets, keys.numel(), values, value_image.numel(), batch_first)
     g = group(batch_sum=s.batch_sum, sync=sync)
@@ -284,6 +284,7 @@ def write_batches(types, keys, key_offsets, value_image, values, batch_first, sy
                        b.seq_counts[:, 0], b.seq_counts[:, 1], last_sequence + (key_offsets.numel() - 1), end)
 
 
+@on_stream
 def write_logs(types, keys, key_offsets, value_image, values, batch_first, sync=None, last_sequence=0,
                write_buffer_size=4 << 20, mem_state=None, log_offset=0, stream=None):
     """DBImpl::Write of every queued writer with MakeRoomForWrite's switch
@@ -301,10 +302,6 @@ def write_logs(types, keys, key_offsets, value_image, values, batch_first, sync=
     the memtable's accounting; pass the returned one to the next call."""
     torch = _torch()
     from . import memtable as _mt
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return write_logs(types, keys, key_offsets, value_image, values, batch_first, sync, last_sequence,
-                              write_buffer_size, mem_state, log_offset)
     dev = key_offsets.device
     s = sizes(types, key_offsets, keys.numel(), values, value_image.numel(), batch_first)
     g = group(batch_sum=s.batch_sum, sync=sync)

@@ -168,12 +168,17 @@ class PlanInput:
         return (self.d_cand, self.d_info, self.d_use, self.d_wb, self.d_ckeys, self.d_coff, self.d_keys, self.d_koff)
 
     def model(self):
-        n = len(self.users)
-        return [bfm.plan(self.kinds, [self.cand[s][q] for s in range(len(self.kinds))], self.use, self.wb,
-                         self.cursors, self.users[q]) for q in range(n)]
+        return plan_model(self.kinds, self.cand, self.use, self.wb, self.cursors, self.users)
 
 
-def random_plan_input(torch, rng, n, n_slots):
+def plan_model(kinds, cand, use, wb, cursors, users):
+    """The probe list of every query, from the model."""
+    return [bfm.plan(kinds, [cand[s][q] for s in range(len(kinds))], use, wb, cursors, users[q])
+            for q in range(len(users))]
+
+
+def random_plan_values(rng, n, n_slots):
+    """(kinds, cand, use, wb, cursors, users) of a random plan input, on the host."""
     kinds = slot_table(rng, n_slots)
     users = [rng.choice((b"", b"k", b"k1", b"k12", b"k123456789", bytes(rng.randrange(256) for _ in range(rng.randrange(12)))))
              for _ in range(n)]
@@ -182,7 +187,11 @@ def random_plan_input(torch, rng, n, n_slots):
     cand = [[rng.choice((0, 1, 2, 2, 2, 3)) for _ in range(n)] for _ in kinds]
     use = [rng.choice((0, 0, 1, 3)) for _ in range(4)]
     wb = [0] + [rng.randrange(2) for _ in range(3)]
-    return PlanInput(torch, kinds, cand, use, wb, cursors, users)
+    return kinds, cand, use, wb, cursors, users
+
+
+def random_plan_input(torch, rng, n, n_slots):
+    return PlanInput(torch, *random_plan_values(rng, n, n_slots))
 
 
 def run_plan(torch, x):

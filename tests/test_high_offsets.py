@@ -58,7 +58,6 @@ builder, merge, pack, memtable (scan and sort), Get (slices_gather,
 lookup_keys) and scans (plan, range).  The snappy and bloom entry points take
 no buffer size, so they have nothing to reject.
 """
-import json
 import os
 
 import numpy as np
@@ -67,8 +66,6 @@ import pytest
 import high_offsets as ho
 from golden import blockmodel as bm
 from high_offsets import ARENA_BYTES, FILL, GUARD, LINE
-from golden.snappy_inputs import block as snappy_block
-from test_block import apply_ops, sampled_targets
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 G = os.path.join(HERE, "golden")
@@ -77,19 +74,7 @@ G = os.path.join(HERE, "golden")
 # --------------------------------------------------------------------------- the cases
 @pytest.fixture(scope="module")
 def block_case():
-    """One good block (internal keys), one with a bad entry, one with long
-    shared prefixes, from block_fixture.json."""
-    fx = json.load(open(os.path.join(G, "block_fixture.json")))
-    built = {r["name"]: bytes.fromhex(r["hex"]) for r in fx["built"]}
-    mut = {r["name"]: r for r in fx["mutated"]}
-    bad = mut["varint5_high_bits_kept"]
-    blocks = [built["internal_i3"], apply_ops(built[bad["base"]], bad["ops"]), built["i16_200"]]
-    assert [bm.walk(b)[0] for b in blocks] == [bm.OK, bm.BAD_ENTRY, bm.OK]
-    probes = []
-    for i, b in enumerate(blocks):
-        keys = [e[0] for e in bm.walk(built[bad["base"]] if i == 1 else b)[1]]
-        probes += [(i, t) for t in sampled_targets(keys, 6)]
-    return ho.block_case(blocks, [True, False, False], probes)
+    return ho.fixture_block_case()
 
 
 BLOCK_MODES = ((bm.BYTEWISE, False), (bm.INTERNAL_KEY, False), (bm.BYTEWISE, True))
@@ -108,32 +93,12 @@ def block_cuts(case):
 
 @pytest.fixture(scope="module")
 def snappy_case(snappy_oracle, snappy_golden):
-    """An incompressible block, one of long copies and an empty one, from
-    snappy_fixture.json's specs."""
-    def pick(kind):
-        return next(c for c in snappy_golden["cases"] if c["kind"] == kind and 600 <= c["n"] <= 5000)
-    rnd, per = pick("random"), pick("period")
-    blocks = [snappy_block("random", rnd["n"], rnd["seed"]), snappy_block("period", per["n"], per["seed"]), b""]
-    streams = [snappy_oracle.compress(b) for b in blocks]
-    assert len(streams[0]) > rnd["n"] and len(streams[1]) < per["n"] // 8
-    d_rnd = snappy_block("random", rnd["n"], rnd["seed"] + 1)
-    for x in range(1, 256):  # the same copy structure over other bytes: the same compressed length
-        d_per = bytes(c ^ x for c in blocks[1])
-        if len(snappy_oracle.compress(d_per)) == len(streams[1]):
-            break
-    dblocks = [d_rnd, d_per, b""]
-    return ho.snappy_case(blocks, streams, dblocks, [snappy_oracle.compress(b) for b in dblocks])
+    return ho.fixture_snappy_case(snappy_oracle, snappy_golden)
 
 
 @pytest.fixture(scope="module")
 def bloom_case(bloom_oracle):
-    def keys(tag, n):
-        return [b"%s%04d" % (tag, i * 7) + b"k" * (i % 5) for i in range(n)]
-    built, absent = keys(b"in", 70), keys(b"no", 70)
-    d_built, d_absent = keys(b"IN", 70), keys(b"NO", 70)
-    # probes: the payload asks for its own keys first, the decoy for them last
-    return ho.bloom_case(built, d_built, built[:40] + absent[:40], d_absent[:40] + d_built[:40],
-                         [0, 1, 30, 70], 10, bloom_oracle)
+    return ho.fixture_bloom_case(bloom_oracle)
 
 
 @pytest.fixture(scope="module")
