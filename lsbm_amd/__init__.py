@@ -30,14 +30,18 @@
   lsbm_amd.buffered LSbM's buffered Get: Builder::SaveTo's sorted-table lists, the slots Version::Get can reach,
                     the probe plan under covered_by_del / covered_by_ins / covered_by_head / checkwb, and
                     table reads by probe rank (BufferedVersion.get, from_manifest)
+  lsbm_amd.rangequery  LSbM's RangeQuery over the buffered tree: the files Version::RangeQuery reads under
+                    checkwb / wb_covered / dl_covered / cb_covered, and TableCache::GetRange's Seek and count
+                    up to the end key over a range index of the opened files (RangeQuery.query)
 
 The compute lives in lsbm_amd/liblsbm_crc32c.so (hand-written gfx950 HIP
 kernels behind the C ABIs in include/lsbm_crc32c.h, include/lsbm_bloom.h, include/lsbm_snappy.h and
 include/lsbm_block.h, include/lsbm_block_build.h, include/lsbm_merge.h, include/lsbm_table_pack.h,
 include/lsbm_memtable.h, include/lsbm_get.h, include/lsbm_iter.h, include/lsbm_write.h, include/lsbm_log_read.h,
-include/lsbm_manifest.h, include/lsbm_probe.h).
+include/lsbm_manifest.h, include/lsbm_probe.h, include/lsbm_range.h).
 """
 from ._lib import LIB_PATH, LsbmError, lib  # noqa: F401
 
 __all__ = ["LIB_PATH", "LsbmError", "lib", "crc32c", "engine", "table", "log", "bloom", "snappy",
-           "block", "block_build", "merge", "sstable", "memtable", "db", "scan", "write", "manifest", "buffered"]
+           "block", "block_build", "merge", "sstable", "memtable", "db", "scan", "write", "manifest", "buffered",
+           "rangequery"]

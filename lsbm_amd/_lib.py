@@ -227,6 +227,16 @@ PROBE_SIGNATURES = {
     "lsbm_probe_emit_dev": (_int, _PROBE_INPUTS + [_vp, _vp, _u64, _vp, _vp]),
 }
 
+# every symbol include/lsbm_range.h declares
+_RANGE_KEYS = [_vp, _u64, _vp, _vp, _u64, _vp, _u64]
+_RANGE_INPUTS = [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp] + _RANGE_KEYS
+RANGE_SIGNATURES = {
+    "lsbm_range_plan_dev": (_int, _RANGE_INPUTS + [_vp, _vp, _vp]),
+    "lsbm_range_emit_dev": (_int, _RANGE_INPUTS + [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "lsbm_range_count_dev": (_int, [_vp, _u64, _vp, _u64, _vp, _vp, _u64] + _RANGE_KEYS
+                             + [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -252,7 +262,8 @@ def lib():
                                   + list(GET_SIGNATURES.items()) + list(ITER_SIGNATURES.items())
                                   + list(WRITE_SIGNATURES.items()) + list(LOG_READ_SIGNATURES.items())
                                   + list(MEMCUT_SIGNATURES.items()) + list(TABLE_WRITE_SIGNATURES.items())
-                                  + list(MANIFEST_SIGNATURES.items()) + list(PROBE_SIGNATURES.items())):
+                                  + list(MANIFEST_SIGNATURES.items()) + list(PROBE_SIGNATURES.items())
+                                  + list(RANGE_SIGNATURES.items())):
             if os.environ.get("LSBM_LIB_PATH") and not hasattr(handle, name):
                 continue  # (an older build for an A/B: only the symbols it has)
             fn = getattr(handle, name)

@@ -26,9 +26,9 @@ largest), and may be empty.  The lists are small metadata and are built by a
 host loop over the added entries.
 
 Out of scope: RefineCompactionBuffer (which sets `visible`; here it is an
-input), Version::RangeQuery and AddIterators over the buffers, SaveTo on a
-non-empty base, LogAndApply, Finalize, PickCompaction, the key and block
-caches, runtime::setReadCursor.
+input), AddIterators over the buffers, SaveTo on a non-empty base,
+LogAndApply, Finalize, PickCompaction, the key and block caches,
+runtime::setReadCursor.  Version::RangeQuery is lsbm_amd/rangequery.py.
 """
 from collections import namedtuple
 
