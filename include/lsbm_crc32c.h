@@ -213,6 +213,11 @@ int lsbm_test_ragged_kernel(int which);
  * the tail queue (the static interleave, the last rows from the queue); -1
  * restores the default (LSBM_FIXED_QUEUE, same values; unset: 2). */
 int lsbm_test_fixed_queue(int on);
+/* Testing / A/B: the fixed-stride kernel's waves per workgroup for 4 KiB and
+ * 64 KiB blocks: 16, 8 or 4 (every other geometry runs 16); -1 restores the
+ * default (LSBM_FIXED_WAVES, same values).  Any other value returns -1.
+ * Needs no device. */
+int lsbm_test_fixed_waves(int waves);
 /* Testing: the tail queue's minimum rows (groups per wave) of a launch and the
  * rows it hands out through the queue, so that small batches reach the tail
  * path; (-1, -1) restores the defaults. */

@@ -55,6 +55,7 @@ SIGNATURES = {
     "lsbm_test_fail_host_pipeline": (_int, [_int]),
     "lsbm_test_ragged_kernel": (_int, [_int]),
     "lsbm_test_fixed_queue": (_int, [_int]),
+    "lsbm_test_fixed_waves": (_int, [_int]),
     "lsbm_test_fixed_tail": (_int, [_int, _int]),
     "lsbm_test_queue_fault": (_int, [_int, _int]),
     "lsbm_test_queue_pool": (_int, [_int]),

@@ -31,7 +31,8 @@ namespace lsbm {
 hipError_t launch_fixed(const uint8_t* base, uint64_t stride, uint32_t rows, uint64_t n_blocks,
                         const uint32_t* init, uint32_t* out, uint32_t flags, uint32_t k_value,
                         const DevConsts* dc, int grid, hipStream_t stream,
-                        uint32_t* heads, uint32_t own_rows, uint32_t* fault, uint32_t* done, uint32_t* busy);
+                        uint32_t* heads, uint32_t own_rows, uint32_t* fault, uint32_t* done, uint32_t* busy,
+                        int waves);
 hipError_t launch_ragged(const RaggedArgs& a, int grid, hipStream_t stream);
 bool ragged_uses_stream(const RaggedArgs& a);
 int set_ragged_policy(int p);
@@ -305,7 +306,7 @@ uint64_t fixed_split_blocks() {
 // the capture's head set while another launch may hold it).
 constexpr int kFixedQueueDefault = 2;    // what -1 / no LSBM_FIXED_QUEUE means
 constexpr uint32_t kFullQueueMinRows = 4;  // mode 1
-constexpr uint32_t kTailMinRows = 8;       // mode 2
+constexpr uint32_t kTailMinRows = 8;       // mode 2, at 16 waves per workgroup (x 16 / waves: the same batch size)
 constexpr uint32_t kTailSixteenths = 2;    // mode 2: tail = rows * kTailSixteenths / 16
 std::atomic<int> g_fixed_queue{-1};  // -1: not read yet; 0 static, 1 full queue, 2 tail queue (lsbm_test_fixed_queue)
 std::atomic<int> g_tail_min_rows{-1}, g_tail_rows{-1};  // lsbm_test_fixed_tail (-1: the constants above)
@@ -348,13 +349,13 @@ uint32_t* set_done(const DeviceState* st, int s) {
 
 // The queue's late start for a launch of `ngroups` groups over `nwaves` waves:
 // K0 >= 1 static rows, or 0 for the static schedule (no queue).
-uint32_t fixed_own_rows(int mode, uint64_t ngroups, uint64_t nwaves) {
+uint32_t fixed_own_rows(int mode, uint64_t ngroups, uint64_t nwaves, int waves) {
   const uint64_t rows = (ngroups + nwaves - 1) / nwaves;
   if (mode == 1) return ngroups >= kFullQueueMinRows * nwaves ? 1u : 0u;
   if (mode != 2) return 0;
   const int hook_min = g_tail_min_rows.load(std::memory_order_relaxed);
   const int hook_tail = g_tail_rows.load(std::memory_order_relaxed);
-  const uint64_t min_rows = hook_min > 0 ? (uint64_t)hook_min : kTailMinRows;
+  const uint64_t min_rows = hook_min > 0 ? (uint64_t)hook_min : kTailMinRows * 16u / (uint32_t)waves;
   if (ngroups < min_rows * nwaves || rows > 0xffffffull) return 0;
   const uint64_t tail = hook_tail > 0 ? (uint64_t)hook_tail : std::max<uint64_t>(1, rows * kTailSixteenths / 16);
   return (uint32_t)(rows > tail ? rows - tail : 1);
@@ -376,9 +377,37 @@ bool sst_pieces_on() {
   return q == 1;
 }
 
-int grid_for(const DeviceState* st, uint64_t n_blocks) {
+// The fixed kernel's waves per workgroup (LSBM_FIXED_WAVES, lsbm_test_fixed_waves):
+// 16, 8 or 4.  A CU runs one workgroup and keeps 128 KiB of row loads in
+// flight whatever the count (crc32c_kernels.hip fixed_bank_rows), so with fewer
+// waves each holds more rows, and a 32 KiB group takes a wave, and a queue item
+// a workgroup, in proportion less time, and the launch's tail is one item long.
+// Measured in one process, alternating passes over one buffer, 50 launches a
+// pass (tools/ab/fixed_waves_inproc.py, DESIGN.md section 4,
+// profiles/r08/fat_waves/), 16 / 8 / 4 waves: config 2 619.6 / 605.9 / 655.1 us
+// per launch, 1M x 64 KiB 9.832 / 9.585 / 10.417 ms, a 10M-block shard 5.892 /
+// 5.757 / 6.289 ms: 8 waves +2.3 to +2.6%, no pass of it as slow as the fastest
+// 16-wave pass; 4 waves -5 to -6% (kept for A/B runs only).  Launches of the
+// compile-time row counts (4 KiB and 64 KiB blocks) only; every other geometry
+// runs 16 waves.
+constexpr int kFixedWavesDefault = 8;
+std::atomic<int> g_fixed_waves{-1};  // -1: not read yet (lsbm_test_fixed_waves)
+int fixed_waves_setting() {
+  int w = g_fixed_waves.load(std::memory_order_relaxed);
+  if (w < 0) {
+    const char* v = getenv("LSBM_FIXED_WAVES");
+    const int e = v ? atoi(v) : 0;
+    w = (e == 16 || e == 8 || e == 4) ? e : kFixedWavesDefault;
+    int expect = -1;
+    if (!g_fixed_waves.compare_exchange_strong(expect, w)) w = expect;
+  }
+  return w;
+}
+int fixed_waves_for(uint32_t rows) { return rows == 32 || rows == 512 ? fixed_waves_setting() : kWavesPerWg; }
+
+int grid_for(const DeviceState* st, uint64_t n_blocks, int waves) {
   const uint64_t groups = (n_blocks + 7) / 8;
-  const uint64_t wgs = (groups + kWavesPerWg - 1) / kWavesPerWg;
+  const uint64_t wgs = (groups + waves - 1) / waves;
   return (int)std::max<uint64_t>(1, std::min<uint64_t>(wgs, (uint64_t)st->num_cus));
 }
 
@@ -486,6 +515,14 @@ int run_ragged(RaggedArgs a, hipStream_t stream) {
 extern "C" __attribute__((visibility("default"))) int lsbm_test_fixed_queue(int on) {
   if (on < -1 || on > 2) return -1;
   g_fixed_queue.store(on);
+  return 0;
+}
+
+// Testing / A/B: the fixed kernel's waves per workgroup for 4 KiB and 64 KiB
+// blocks, 16, 8 or 4; -1 back to LSBM_FIXED_WAVES's default.  Needs no device.
+extern "C" __attribute__((visibility("default"))) int lsbm_test_fixed_waves(int waves) {
+  if (waves != -1 && waves != 16 && waves != 8 && waves != 4) return -1;
+  g_fixed_waves.store(waves);
   return 0;
 }
 
@@ -628,12 +665,13 @@ __attribute__((visibility("default"))) int lsbm_crc32c_fixed_dev(
       f += m;
     }
     uint32_t* heads = nullptr;
-    const uint64_t nwaves = (uint64_t)st->num_cus * kWavesPerWg;
+    const int waves = fixed_waves_for((uint32_t)(len / kRowBytes));
+    const uint64_t nwaves = (uint64_t)st->num_cus * waves;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     // (every launch by the smallest one's rule: one decision per call)
     const int qmode = fixed_queue_mode();
     std::vector<int> sets;  // pooled head sets, one per launch
-    if (fixed_own_rows(qmode, (min_m + 7) / 8, nwaves) != 0 && hipStreamIsCapturing(hs, &cap) == hipSuccess &&
+    if (fixed_own_rows(qmode, (min_m + 7) / 8, nwaves, waves) != 0 && hipStreamIsCapturing(hs, &cap) == hipSuccess &&
         cap == hipStreamCaptureStatusNone) {
       for (uint64_t i = 0; i < launches; i++) {
         const int sidx = take_head_set(st);
@@ -662,9 +700,10 @@ __attribute__((visibility("default"))) int lsbm_crc32c_fixed_dev(
       uint32_t* const h = pooled ? set_heads(st, sets[li]) : heads ? heads + li * kQueueWords : nullptr;
       e = launch_fixed(static_cast<const uint8_t*>(d_base) + f * stride, stride,
                        (uint32_t)(len / kRowBytes), m, d_init ? d_init + f : nullptr, d_out + f, flags,
-                       k_value, st->d_consts, grid_for(st, m), hs, h,
-                       h ? fixed_own_rows(qmode, (m + 7) / 8, nwaves) : 1u, st->cap_word,
-                       pooled ? set_done(st, sets[li]) : nullptr, pooled ? st->pool_busy + sets[li] : nullptr);
+                       k_value, st->d_consts, grid_for(st, m, waves), hs, h,
+                       h ? fixed_own_rows(qmode, (m + 7) / 8, nwaves, waves) : 1u, st->cap_word,
+                       pooled ? set_done(st, sets[li]) : nullptr, pooled ? st->pool_busy + sets[li] : nullptr,
+                       waves);
       if (e != hipSuccess && pooled)  // (this launch's set and the later ones': never launched on)
         for (uint64_t k = li; k < launches; k++) release_head_set(st, sets[k]);
       f += m;

@@ -35,11 +35,15 @@ extern "C" __attribute__((visibility("default"))) int lsbm_diag_stamps(uint64_t*
 #ifndef LSBM_PF
 #define LSBM_PF 4
 #endif
-constexpr uint32_t kPF = LSBM_PF;  // rows per load bank
+// Rows per load bank of the fixed kernel at W waves per workgroup: LSBM_PF at
+// 16 waves and in proportion more at fewer, so that a workgroup (a CU) keeps
+// the same 2 banks x 64 rows x 1 KiB = 128 KiB of loads in flight.
+constexpr uint32_t fixed_bank_rows(uint32_t waves) { return LSBM_PF * 16u / waves; }
 
 
 constexpr int kAuxNT = 2;     // buffer-load cache policy: non-temporal (read-once stream)
 
+// (LOAD_BANK, ABSORB: kPF is the kernel's fixed_bank_rows(kWavesPerWg).)
 // Issue the loads of rows [r0, r0 + kPF) of this lane's slice into bank X.
 // Rows past the end re-read the last row (clamped, a cache hit), so the
 // number of loads in flight is static and the compiler's vmcnt waits exact.
@@ -65,9 +69,14 @@ constexpr int kAuxNT = 2;     // buffer-load cache policy: non-temporal (read-on
 // ---------------------------------------------------------------------------
 // Fixed-stride kernel.  Each wave takes 8 consecutive blocks at a time (one per
 // 8-lane group); waves stride through the batch.  rows = len / 128.
+// kWavesPerWg (here the kernel's own, not crc32c_types.h's 16): the waves of a
+// workgroup, 16, 8 or 4.  Fewer waves hold in proportion more rows per bank,
+// so a group takes a wave, and a queue item a workgroup, in proportion less
+// time: the launch's tail, one item long, shrinks with them (DESIGN.md
+// section 4).
 // ---------------------------------------------------------------------------
-template <bool kHasInit, uint32_t kRows>
-__global__ __launch_bounds__(kBlockThreads) void crc32c_fixed_kernel(
+template <bool kHasInit, uint32_t kRows, uint32_t kWavesPerWg>
+__global__ __launch_bounds__(kWavesPerWg * kWaveLanes) void crc32c_fixed_kernel(
     const uint8_t* __restrict__ base, uint64_t stride, uint32_t rows_arg, uint64_t n_blocks,
     const uint32_t* __restrict__ init, uint32_t* __restrict__ out, uint32_t flags,
     uint32_t k_value /* A^len(~0) ^ ~0: the init term of crc32c::Value */,
@@ -75,6 +84,8 @@ __global__ __launch_bounds__(kBlockThreads) void crc32c_fixed_kernel(
     uint32_t own_rows /* the queue's late start: static rows before its items, >= 1 */,
     uint32_t* __restrict__ fault /* the queue's sticky spin-cap word */,
     uint32_t* __restrict__ done, uint32_t* __restrict__ busy /* pooled heads: handed back zeroed (WgQueue::leave) */) {
+  static_assert(kWavesPerWg == 16 || kWavesPerWg == 8 || kWavesPerWg == 4, "64 rows in flight per bank and CU");
+  constexpr uint32_t kPF = fixed_bank_rows(kWavesPerWg);
   const uint32_t rows = kRows ? kRows : rows_arg;  // kRows != 0: fully unrolled
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t g = lane >> 3, li = lane & 7u;
@@ -106,7 +117,7 @@ __global__ __launch_bounds__(kBlockThreads) void crc32c_fixed_kernel(
     asm volatile("" : "+v"(loff));  // defined in every lane (see crc32c_units_kernel)
   };
   // Interleave: wave w starts at group w; a workgroup's k-th group is
-  // (k / 16) * nwaves + 16 * blockIdx + k % 16, so at any moment the GPU
+  // (k / W) * nwaves + W * blockIdx + k % W (W waves), so at any moment the GPU
   // streams one contiguous window of the batch.  (A dynamic per-XCC work
   // queue in global memory was 5% slower end to end: DESIGN.md section 4.)
 #ifndef LSBM_WG_STATIC
@@ -151,7 +162,7 @@ __global__ __launch_bounds__(kBlockThreads) void crc32c_fixed_kernel(
     if (kRows == 0 || kPF < rows) LOAD_BANK(b, kPF);
     loaded = true;
   }
-  load_lds_tables(g_lds, dc);
+  load_lds_tables<kWavesPerWg * kWaveLanes>(g_lds, dc);
   DIAG_STAMP(1);
 
   // a batch this wave publishes: batch 1 by the taker of slot 0 of row own_rows - 1
@@ -439,20 +450,31 @@ __global__ __launch_bounds__(kBlockThreads) void stream_read_kernel(const uint8_
 hipError_t launch_fixed(const uint8_t* base, uint64_t stride, uint32_t rows, uint64_t n_blocks,
                         const uint32_t* init, uint32_t* out, uint32_t flags, uint32_t k_value,
                         const DevConsts* dc, int grid, hipStream_t stream, uint32_t* heads, uint32_t own_rows,
-                        uint32_t* fault, uint32_t* done, uint32_t* busy) {
-#define LSBM_LAUNCH_FIXED(HI, R)                                                        \
-  hipLaunchKernelGGL((crc32c_fixed_kernel<HI, R>), dim3(grid), dim3(kBlockThreads), 0, stream, \
-                     base, stride, rows, n_blocks, init, out, flags, k_value, dc, heads, own_rows, fault, done, busy)
-  // compile-time row counts for the SSTable-sized configs: 4 KiB and 64 KiB
+                        uint32_t* fault, uint32_t* done, uint32_t* busy, int waves) {
+#define LSBM_LAUNCH_FIXED(HI, R, W)                                                                       \
+  hipLaunchKernelGGL((crc32c_fixed_kernel<HI, R, W>), dim3(grid), dim3(W * kWaveLanes), 0, stream, base, \
+                     stride, rows, n_blocks, init, out, flags, k_value, dc, heads, own_rows, fault, done, busy)
+  // compile-time row counts for the SSTable-sized configs, 4 KiB and 64 KiB, at
+  // 16, 8 or 4 waves per workgroup; any other row count at 16 (with longer
+  // banks a short block would issue more clamped loads)
+#define LSBM_LAUNCH_FIXED_ROWS(HI, R)                 \
+  do {                                                \
+    if (waves == 16) LSBM_LAUNCH_FIXED(HI, R, 16);    \
+    else if (waves == 8) LSBM_LAUNCH_FIXED(HI, R, 8); \
+    else if (waves == 4) LSBM_LAUNCH_FIXED(HI, R, 4); \
+    else return hipErrorInvalidValue;                 \
+  } while (0)
+  if (rows != 32 && rows != 512 && waves != 16) return hipErrorInvalidValue;
   if (init) {
-    if (rows == 32) LSBM_LAUNCH_FIXED(true, 32);
-    else if (rows == 512) LSBM_LAUNCH_FIXED(true, 512);
-    else LSBM_LAUNCH_FIXED(true, 0);
+    if (rows == 32) LSBM_LAUNCH_FIXED_ROWS(true, 32);
+    else if (rows == 512) LSBM_LAUNCH_FIXED_ROWS(true, 512);
+    else LSBM_LAUNCH_FIXED(true, 0, 16);
   } else {
-    if (rows == 32) LSBM_LAUNCH_FIXED(false, 32);
-    else if (rows == 512) LSBM_LAUNCH_FIXED(false, 512);
-    else LSBM_LAUNCH_FIXED(false, 0);
+    if (rows == 32) LSBM_LAUNCH_FIXED_ROWS(false, 32);
+    else if (rows == 512) LSBM_LAUNCH_FIXED_ROWS(false, 512);
+    else LSBM_LAUNCH_FIXED(false, 0, 16);
   }
+#undef LSBM_LAUNCH_FIXED_ROWS
 #undef LSBM_LAUNCH_FIXED
   return hipGetLastError();
 }

@@ -61,7 +61,7 @@ def fixed(entry, L, n, seed, reps):
     o = oracle()
     bad = sum(int(got[b] != o.value(stream_bytes(seed, int(b) * L, L).tobytes()))
               for b in np.random.default_rng(1).choice(n, 32, replace=False))
-    line(entry, rf"crc32c_fixed_kernel<false, {512 if L == 65536 else 32}u>", n * L, t, bad,
+    line(entry, rf"crc32c_fixed_kernel<false, {512 if L == 65536 else 32}u, \d+u>", n * L, t, bad,
          blocks=n, block_bytes=L)
 
 

@@ -13,7 +13,7 @@ import sys
 
 out = sys.argv[1]
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEAD = "crc32c_fixed_kernel<false, 32u>"
+HEAD = "crc32c_fixed_kernel<false, 32u, "  # (any waves per workgroup)
 
 
 def counters(d):

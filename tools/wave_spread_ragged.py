@@ -14,7 +14,8 @@ Entries:
   sst_verify  1M x 4,118-B SSTable blocks, lsbm_sst_verify_dev  -> crc32c_units_kernel<40,SstVerify>
   sst_crcs    the same image, lsbm_sst_trailer_crcs_dev         -> crc32c_units_kernel<40,SstCrc>
   sst_seal    the same image, lsbm_sst_seal_dev                 -> crc32c_units_kernel<40,SstCrc> + trailers
-  fixed4k     config 2, for comparison                          -> crc32c_fixed_kernel<false,32>
+  fixed4k     config 2, for comparison                          -> crc32c_fixed_kernel<false,32,W>
+              (W waves per workgroup by LSBM_FIXED_WAVES; reported as waves_per_wg, from the stamps)
 One JSON line per entry: the launch span, the waves' durations (mean, CV),
 when the first wave finished (fraction of the span: the GPU is partly idle
 from there on) and the spread of the waves' ends.
@@ -35,7 +36,7 @@ sys.path.insert(0, HERE)
 from bench_configs import zipf_lengths  # noqa: E402
 
 
-def timeline(st, alg_bytes):
+def timeline(st, alg_bytes, wpw=None):
     nw = int(np.count_nonzero(st[2]))
     start, first, end = (st[k][:nw].astype(np.int64) for k in range(3))
     t0 = start.min()
@@ -44,7 +45,8 @@ def timeline(st, alg_bytes):
     endr = (end - t0) / 100.0
     setup = (first - start) / 100.0
     xcc = st[3][:nw].astype(np.int64)
-    wpw = int(os.environ.get("LSBM_WAVES_PER_WG", "16"))
+    if wpw is None:
+        wpw = int(os.environ.get("LSBM_WAVES_PER_WG", "16"))
     wg = np.arange(nw) // wpw
     ngw = nw // wpw
     wg_end = np.array([endr[wg == g].max() for g in range(ngw)])
@@ -54,7 +56,7 @@ def timeline(st, alg_bytes):
     extra = {"by_xcc_mean_end_dur_us": by_xcc,
              "wg_end_p0_p50_p100_us": [round(float(x), 1) for x in np.percentile(wg_end, [0, 50, 100])],
              "within_wg_end_spread_mean_us": round(float(wg_in.mean()), 1)}
-    return {"waves": nw, **extra, "span_us": round(float(span), 1),
+    return {"waves": nw, "waves_per_wg": wpw, **extra, "span_us": round(float(span), 1),
             "GBps_span": round(alg_bytes / (span / 1e6) / 1e9, 1),
             "pct_hbm_span": round(100 * alg_bytes / (span / 1e6) / 8e12, 2),
             "start_spread_us": round(float((start - t0).max() / 100.0), 1),
@@ -67,7 +69,7 @@ def timeline(st, alg_bytes):
             "tail_frac": round(float((span - endr.min()) / span), 4)}
 
 
-def run(entry, lb, stamps_fn, launch, alg, reps=3):
+def run(entry, lb, stamps_fn, launch, alg, reps=3, wgs=None):
     import torch
     st = np.zeros((4, 65536), dtype=np.uint64)
     t0 = time.perf_counter()
@@ -80,7 +82,8 @@ def run(entry, lb, stamps_fn, launch, alg, reps=3):
         st[:] = 0
         assert stamps_fn(st.ctypes.data, 4 * 65536) == 0
         rec = {"entry": entry, "rep": r, "algorithmic_bytes": int(alg)}
-        rec.update(timeline(st, alg))
+        # wgs: the launch's workgroups, where its waves per workgroup are a run-time setting
+        rec.update(timeline(st, alg, int(np.count_nonzero(st[2])) // wgs if wgs else None))
         print(json.dumps(rec), flush=True)
         dump = os.environ.get("LSBM_STAMPS_DUMP")  # a directory: the raw stamps per entry and rep
         if dump:
@@ -109,7 +112,9 @@ def main():
         d = torch.empty(n * L, dtype=torch.uint8, device="cuda")
         engine.fill_splitmix64(d, 0x5EED0000)
         out = torch.empty(n, dtype=torch.int32, device="cuda")
-        run("fixed4k", lb, units, lambda: engine.crc32c_fixed(d, L, L, n, out=out, stream=s), n * L)
+        # (one workgroup per CU at this size; 16, 8 or 4 waves each: LSBM_FIXED_WAVES)
+        run("fixed4k", lb, units, lambda: engine.crc32c_fixed(d, L, L, n, out=out, stream=s), n * L,
+            wgs=torch.cuda.get_device_properties(0).multi_processor_count)
         del d, out
     if any(e.startswith("sst") for e in entries):
         n, L = 1 << 20, 4118
